@@ -4,6 +4,12 @@ whole node), bf16, synthetic data, random-init weights, synchronous data
 parallelism over RCCL (one process per MI355X).
 
     python bench.py --gpus N --steps K --warmup W [--batch B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+--dump-outputs DIR then also writes what the last timed step computed (see
+dump_outputs).  --full is where measurements beyond the headline figure
+belong; a one-GPU run has none today.
 
 For N > 1 the driver launches it under torch.distributed.run (one rank per
 GPU).  Started with --gpus N > 1 and no WORLD_SIZE, it spawns the N ranks
@@ -62,6 +68,14 @@ def main():
     ap.add_argument("--mark-steps", action="store_true",
                     help="bracket the timed steps with hvk_trace_marker "
                          "kernels (step-only rocprofv3 summaries)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one "
+                         "computed (parameters, the net's output, the "
+                         "evaluator's error signal and metrics) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond "
+                         "the headline figure (nothing at one GPU today)")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 512 if args.model == "vgg16" else 3072
@@ -164,6 +178,8 @@ def main():
             wf.run_steps(args.stats_steps)
         sync()
     dp_info = dp_report(dp, store, backend, wf)
+    if args.dump_outputs and dp.rank == 0:
+        dump_outputs(wf, args.dump_outputs)
     if dp.rank == 0:
         base = None
         try:
@@ -206,6 +222,61 @@ def main():
         wd.stop()
     dp.shutdown()
     return 0
+
+
+# --dump-outputs: bytes over all files (the limit is 64 MB; the .npy headers
+# take the rest), and the seed of the sample taken from a larger array
+DUMP_BUDGET = 48 << 20
+DUMP_SEED = 2024
+
+
+def step_outputs(wf):
+    """[(name, tensor)] of what a training step hands its caller: every
+    layer's float32 master weights and bias after the update, the last
+    layer's output for the step's minibatch, the evaluator's error signal
+    and its accumulated metrics."""
+    import re
+    out = []
+    for i, u in enumerate(wf.forwards):
+        if getattr(u, "_pw_", None) is None:
+            continue
+        # the layer's position keeps the names of unnamed layers apart
+        name = "%02d_%s" % (i, re.sub(r"\W", "_", str(u.name)))
+        out.append((name + "_weights", u.weights_master))
+        if u.bias_master is not None:
+            out.append((name + "_bias", u.bias_master))
+    out.append(("output", wf.forwards[-1].output.devmem))
+    ev = wf.evaluator
+    if ev.err_output.devmem is not None:
+        out.append(("err_output", ev.err_output.devmem))
+    if ev.metrics_ is not None:
+        out.append(("metrics", ev.metrics_))
+    return out
+
+
+def dump_outputs(wf, directory):
+    """Write step_outputs(wf) as ``directory/<name>.npy`` (float32).  The
+    files share DUMP_BUDGET bytes: small arrays are written whole, in their
+    own shape; the larger ones split what is left evenly, each as a 1-D
+    sample at sorted indices drawn from numpy.random.RandomState(DUMP_SEED
+    + its position in the list) - the same elements in every run."""
+    import numpy
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    arrays = step_outputs(wf)
+    left, share = DUMP_BUDGET // 4, {}
+    by_size = sorted(range(len(arrays)), key=lambda i: arrays[i][1].numel())
+    for k, i in enumerate(by_size):
+        share[i] = min(arrays[i][1].numel(), left // (len(by_size) - k))
+        left -= share[i]
+    for i, (name, t) in enumerate(arrays):
+        t = t.detach()
+        if share[i] < t.numel():
+            idx = numpy.sort(numpy.random.RandomState(DUMP_SEED + i).randint(
+                0, t.numel(), share[i]))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        numpy.save(os.path.join(directory, name + ".npy"),
+                   t.float().cpu().numpy())
 
 
 def _spawn(args):

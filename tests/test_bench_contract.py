@@ -155,6 +155,96 @@ def test_bench_refuses_mismatched_world_size():
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 
+def _bench_cpu(*extra):
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--cpu", "--model",
+           "lenet", "--batch", "8", "--steps", "3", "--warmup", "1",
+           "--steps-per-epoch", "2"] + list(extra)
+    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, OMP_NUM_THREADS="2"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_repeat_and_full(tmp_path):
+    """--dump-outputs DIR writes the last timed step's arrays as float32
+    DIR/<name>.npy; the same arguments give the same inputs, so a second run
+    (here with --full, which adds nothing to a one-rank run) writes the same
+    arrays - up to the float32 rounding of a reduction whose order the CPU
+    thread pool may change."""
+    import numpy
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    d = _bench_cpu("--dump-outputs", a)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(8 / (d["ms_per_step"] / 1e3), rel=0.02)
+    d2 = _bench_cpu("--dump-outputs", b, "--full")
+    assert set(d2) == set(d)
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b))
+    assert "output.npy" in names and "metrics.npy" in names
+    assert len([n for n in names if n.endswith("_weights.npy")]) == 4
+    assert all(n.endswith(".npy") for n in names)
+    for n in names:
+        x, y = numpy.load(os.path.join(a, n)), numpy.load(os.path.join(b, n))
+        assert x.dtype == numpy.float32 and x.size > 0, n
+        assert numpy.isfinite(x).all(), n
+        numpy.testing.assert_allclose(x, y, rtol=1e-5, atol=1e-7, err_msg=n)
+    out = numpy.load(os.path.join(a, "output.npy"))
+    assert out.shape == (8, 10)
+    numpy.testing.assert_allclose(out.sum(1), 1.0, rtol=1e-5)
+
+
+def test_bench_dump_outputs_samples_within_the_budget(tmp_path):
+    """Arrays that do not fit share the byte budget as fixed seeded samples;
+    the small ones are written whole."""
+    import types
+    import numpy
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    n_big = bench.DUMP_BUDGET // 4        # two of these are twice the budget
+
+    def unit(name, w, b):
+        return types.SimpleNamespace(name=name, _pw_=object(),
+                                     weights_master=w, bias_master=b)
+    big1 = torch.rand(n_big, generator=g)
+    big2 = torch.rand(2, n_big // 2, generator=g).to(torch.bfloat16)
+    small = torch.rand(7, 5, generator=g)
+    wf = types.SimpleNamespace(
+        forwards=[unit("a", big1, torch.ones(3)),
+                  types.SimpleNamespace(name="pool"),
+                  unit("b c", big2, None),
+                  types.SimpleNamespace(name="last", _pw_=None,
+                                        output=types.SimpleNamespace(
+                                            devmem=small))],
+        evaluator=types.SimpleNamespace(
+            err_output=types.SimpleNamespace(devmem=None),
+            metrics_=torch.zeros(3, 3)))
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.dump_outputs(wf, a)
+    bench.dump_outputs(wf, b)
+    names = sorted(os.listdir(a))
+    assert names == ["00_a_bias.npy", "00_a_weights.npy", "02_b_c_weights.npy",
+                     "metrics.npy", "output.npy"]
+    total = sum(os.path.getsize(os.path.join(a, n)) for n in names)
+    assert bench.DUMP_BUDGET * 0.9 < total <= 64 * 10 ** 6
+    got = {n: numpy.load(os.path.join(a, n)) for n in names}
+    for n in names:
+        assert got[n].dtype == numpy.float32
+        numpy.testing.assert_array_equal(got[n],
+                                         numpy.load(os.path.join(b, n)))
+    numpy.testing.assert_array_equal(got["output.npy"], small.numpy())
+    numpy.testing.assert_array_equal(got["00_a_bias.npy"], numpy.ones(3))
+    # a sample holds elements of its array, in the array's order
+    s = got["00_a_weights.npy"]
+    assert s.ndim == 1 and n_big // 3 < s.size < n_big
+    assert numpy.isin(s[:1000], big1.numpy()).all()
+    s2 = got["02_b_c_weights.npy"]
+    assert numpy.isin(s2[:1000], big2.float().numpy()).all()
+
+
 def test_watchdog_and_fault_hooks_fire_on_a_real_workflow():
     """The hooks sit on the decision unit's scheduled dispatch (do_run),
     not only on a direct run() call: a real workflow kicks once per step."""

@@ -147,11 +147,14 @@ def test_background_daemonizes(wf_file, tmp_path):
     assert time.time() - t0 < 150
 
 
-def test_manhole_serves_a_console_on_sigusr2(tmp_path):
+def test_manhole_serves_a_console_on_sigusr2(tmp_path, monkeypatch):
     from veles_amd.dummy import DummyWorkflow
     from veles_amd.interaction import install_manhole
     wf = DummyWorkflow()
-    path = str(tmp_path / "mh.sock")
+    # a name relative to the working directory: an AF_UNIX address holds
+    # ~107 bytes, fewer than a deep temporary directory's absolute path
+    monkeypatch.chdir(tmp_path)
+    path = "mh.sock"
     old = signal.getsignal(signal.SIGUSR2)
     try:
         assert install_manhole(wf, path) == path

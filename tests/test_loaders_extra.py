@@ -169,14 +169,13 @@ def test_hdf5_loader_reports_missing_h5py():
 _ = torch
 
 
-REF_WINE = "/root/reference/veles/tests/res/wine_ensemble.json"
+REF_WINE = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                        "golden", "wine_ensemble.json")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_WINE),
-                    reason="reference fixture absent")
 def test_ensemble_loader_on_reference_wine_results():
     """The reference's own --ensemble-train result file (3 wine models,
-    178 test outputs each; veles/tests/res/wine_ensemble.json): test mode
+    178 test outputs each; veles/tests/res/wine_ensemble.json, stored under tests/golden): test mode
     stacks the members' outputs per sample; with labels (the members'
     consensus here: the reference file holds no ground truth) it trains an
     ensemble-of-outputs classifier input."""

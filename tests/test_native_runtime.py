@@ -3,6 +3,7 @@ by Workflow.package_export must produce the same forward pass in C++ as the
 Python units (reference test strategy: libVeles/tests/workflow_loader.cc,
 memory_optimizer.cc)."""
 import json
+import os
 import subprocess
 import zipfile
 
@@ -153,9 +154,10 @@ def test_native_forward_gpu_matches_cpu(tmp_path):
 
 
 # The reference's own fixtures (libVeles/tests/workflow_files, exported by
-# the reference from its MNIST workflow): the runtime must load both archive
-# formats and compute the forward the packaged arrays define.
-REF_FIX = "/root/reference/libVeles/tests/workflow_files"
+# the reference from its MNIST workflow; stored under tests/golden): the
+# runtime must load both archive formats and compute the forward the packaged
+# arrays define.
+REF_FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _numpy_forward_from_package(pkg, x):
@@ -189,8 +191,6 @@ def _numpy_forward_from_package(pkg, x):
     return h.astype(numpy.float32)
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir(REF_FIX),
-                    reason="reference fixtures absent")
 @pytest.mark.parametrize("name", ["mnist.zip", "mnist.tar.gz"])
 @pytest.mark.parametrize("threads", [0, 3])
 def test_reference_fixture_packages(tmp_path, name, threads):
@@ -236,8 +236,6 @@ def test_native_branch_streams_and_graph_on_gpu():
 @pytest.mark.gpu
 def test_native_reference_fixture_gpu_graph(tmp_path):
     pkg = REF_FIX + "/mnist.zip"
-    if not __import__("os").path.exists(pkg):
-        pytest.skip("reference fixtures absent")
     x = numpy.random.RandomState(8).uniform(0, 1, (64, 784)).astype(
         numpy.float32)
     ref = _numpy_forward_from_package(pkg, x)
