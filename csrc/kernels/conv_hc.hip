@@ -81,6 +81,7 @@ struct HcGeom {
   int flip;           // backward-data: weight tap T - 1 - t
   int ts;             // conv_hc32: epilogue stores staged through LDS
   FastDiv fOW, fOHW, fHPd, fWp;
+  FastDiv fNT, fG;    // conv_hc32: the item decode
 };
 
 // KH x KW taps, KHS kh rows per K stage (a 5 x 5 splits into 3 + 2 rows:
@@ -591,7 +592,12 @@ conv_hc_kernel(const uint16_t* __restrict__ src,
 // DMA after the first stage, 2 the next stage's DMA all at the first k-step,
 // 4 no MFMAs, 8 no stage-end DMA wait, 16 the DMA spread over every k-step,
 // 32 no epilogue stores, 64 no epilogue at all (1, 4, 8, 32, 64 give wrong
-// results by design)
+// results by design); 128 hand-over stamps (correct results): wave 0 of every
+// workgroup reads the clock at each stage barrier's exit and when the
+// fragments of the first MFMA after it have landed, and adds to g_hc_stamps
+// (hvk_hc_stamps) the sums over its stages of {barrier -> first MFMA,
+// barrier -> next barrier, the same two for the stages that follow an
+// epilogue, the two stage counts}
 // MI: 32-pixel m-tiles per wave.  MI 2 with 8 waves (two per SIMD, 64 x
 // NJ * 32 wave tiles).  MI 4 with 4 waves (one per SIMD, 128 x 128 wave
 // tiles, accumulators in the AGPR half: a third less LDS read traffic per
@@ -603,8 +609,37 @@ conv_hc_kernel(const uint16_t* __restrict__ src,
 // stage's taps rotated by T / 2 (0.1-0.9x: the doubled k-loop); s_setprio 1
 // on them (+-2 %); a branch-free DMA issue with idle slots sent to a scratch
 // piece (0.95-0.99x: the extra DMAs cost more than the branches).
+//
+// Stage hand-over (HO; hvk_hc32_handover, 0 = the round-6 order kept for A/B
+// runs).  Round 6 ended every stage in vmcnt(0) + s_barrier and only then
+// ran next() / decode() / prepare() (two runtime divisions per stage) and the
+// first fragment reads, with all eight waves aligned by the barrier and the
+// MFMA pipe empty.  HO:
+//   * an item is decoded once (fNT / fG fast divisions), when its first stage
+//     is prepared; its (tile, group, n-tile) and the running weight offset
+//     stay in scalars and the other stages' prepare is a few adds;
+//   * next() / prepare() of the stage after the one in flight run in the
+//     k-loop's tail, right after the stage's last DMA slot (k-step KB), so
+//     they issue in the shadow of the MFMAs; pwb[] and d_* are dead there;
+//   * on a stage that is not its item's last, the wave waits lgkmcnt(0)
+//     (its reads of cur, the last k-step's fragments among them, are done)
+//     and vmcnt(0) (its DMA pieces into nxt landed) BEFORE the last k-step's
+//     MFMAs, takes the barrier there, issues the next stage's k-step-0
+//     reads from nxt and only then the last k-step's MFMAs; the next k-loop
+//     finds its fragments on the way.  No DMA slot may follow that barrier
+//     (NKSD <= T - 1).  An item's last stage keeps the round-6 order (the
+//     epilogue reuses the fragment registers), then issues the reads.
+// Every wave takes one barrier per stage (+ the staged-store one per item)
+// in both orders; q, last and more1 are workgroup-uniform.  The taps are
+// accumulated in the same order: results are bit-identical.
+// EMC: the epilogue (EM below) as a compile-time choice, -1 the run-time
+// ladder of round 6 (HO 0).  The strict-ReLU instantiations then carry none
+// of the generic activation code and constants.
+#ifdef HVK_HC_ABL
+__device__ unsigned long long g_hc_stamps[8];
+#endif
 template <int KH, int KW, int WM, int WN, int NJ, int NBW, int ABL = 0,
-          int MI = 2, bool TS = false>
+          int MI = 2, bool TS = false, bool HO = false, int EMC = -1>
 __global__ void __attribute__((
     amdgpu_flat_work_group_size(64 * WM * WN, 64 * WM * WN),
     amdgpu_waves_per_eu(WM * WN / 4, WM * WN / 4)))
@@ -661,10 +696,9 @@ conv_hc32_kernel(const uint16_t* __restrict__ src,
   uint32_t pwb[NBW];
   uint32_t d_cofs = 0, d_wofs = 0, d_bofs = 0;
   bool d_bias = false;
-  auto prepare = [&](int it, int q) __attribute__((always_inline)) {
-    int ptl, gi, nt;
-    decode(it, ptl, gi, nt);
-    if (q == 0) {   // wave-uniform: a new item
+  // the window pieces' source offsets of a new item (lane work)
+  auto window = [&](int ptl, int gi) __attribute__((always_inline)) {
+    {
       const uint32_t p0 = (uint32_t)ptl * TPX;
       const uint32_t n0 = fdiv(p0, g.fOHW);
       const uint32_t oh0 = fdiv(p0 - n0 * (uint32_t)g.OHW, g.fOW);
@@ -697,11 +731,44 @@ conv_hc32_kernel(const uint16_t* __restrict__ src,
                     : kBufOOB;
       }
     }
+  };
+  auto prepare = [&](int it, int q) __attribute__((always_inline)) {
+    int ptl, gi, nt;
+    decode(it, ptl, gi, nt);
+    if (q == 0) window(ptl, gi);   // wave-uniform: a new item
     d_cofs = (uint32_t)q * 32u;
     d_wofs = (uint32_t)(((gi * g.NT + nt) * NQ + q) * WB);
     d_bias = bias && q == NQ - 1 && w == 0;
     d_bofs = lane < BN / 4 ? (uint32_t)(gi * g.OCg + nt * BN + 4 * lane) * 4u
                            : kBufOOB;
+  };
+  // HO: (tile, group, n-tile) of the item in the k-loop (c_*) and of the
+  // newest item prepared (n_*: the same item, or the one that follows it);
+  // an item is decoded once, the stages after its first advance d_wofs
+  int c_ptl = 0, c_gi = 0, c_nt = 0, n_ptl = 0, n_gi = 0, n_nt = 0;
+  // the lane work of a new item.  In the k-loop's tail where the registers
+  // allow; the 128-channel tile spills there (both fragment halves are
+  // live) and runs it after the stage's last MFMA is issued
+  constexpr bool WTAIL = MI * NJ <= 6;
+  auto prepare_lanes = [&]() __attribute__((always_inline)) {
+    window(n_ptl, n_gi);
+    d_bofs = lane < BN / 4
+                 ? (uint32_t)(n_gi * g.OCg + n_nt * BN + 4 * lane) * 4u
+                 : kBufOOB;
+  };
+  auto prepare_ho = [&](int it, int q) __attribute__((always_inline)) {
+    if (q == 0) {   // wave-uniform: a new item
+      const uint32_t r = fdiv((uint32_t)it, g.fNT);
+      n_nt = it - (int)r * g.NT;
+      n_ptl = (int)fdiv(r, g.fG);
+      n_gi = (int)r - n_ptl * g.G;
+      if constexpr (WTAIL) prepare_lanes();
+      d_wofs = (uint32_t)((n_gi * g.NT + n_nt) * NQ * WB);
+    } else {
+      d_wofs += (uint32_t)WB;
+    }
+    d_cofs = (uint32_t)q * 32u;
+    d_bias = bias && q == NQ - 1 && w == 0;
   };
   constexpr int NSLOT = NBW + NWW + 1;
   const __amdgpu_buffer_rsrc_t rbias = dma_rsrc(bias);
@@ -740,7 +807,11 @@ conv_hc32_kernel(const uint16_t* __restrict__ src,
   const uint32_t wp32 = (uint32_t)g.Wp * 32u;
   auto slots = [&](int it) __attribute__((always_inline)) {
     int ptl, gi, nt;
-    decode(it, ptl, gi, nt);
+    if constexpr (HO) {   // the newest item prepared
+      ptl = n_ptl;
+    } else {
+      decode(it, ptl, gi, nt);
+    }
     const uint32_t p0 = (uint32_t)ptl * TPX;
     const uint32_t n0 = fdiv(p0, g.fOHW);
     const uint32_t oh0 = fdiv(p0 - n0 * (uint32_t)g.OHW, g.fOW);
@@ -781,7 +852,15 @@ conv_hc32_kernel(const uint16_t* __restrict__ src,
       it += nwg;
     }
   };
-  prepare(item, 0);
+  if constexpr (HO) {
+    prepare_ho(item, 0);
+    if constexpr (!WTAIL) prepare_lanes();
+    c_ptl = n_ptl;
+    c_gi = n_gi;
+    c_nt = n_nt;
+  } else {
+    prepare(item, 0);
+  }
 #pragma unroll
   for (int q = 0; q < NSLOT; ++q) issue_slot(q, 0, true);
   slots(item);
@@ -791,7 +870,14 @@ conv_hc32_kernel(const uint16_t* __restrict__ src,
   int it1 = item, q1 = 0;
   next(it1, q1);
   bool more1 = it1 < g.items;
-  if (more1) prepare(it1, q1);
+  if constexpr (HO) {
+    prepare_ho(it1, q1);   // q1 = 1: the same item (NQ >= 3)
+  } else {
+    if (more1) prepare(it1, q1);
+  }
+  // HO: the stage after (it1, q1), prepared in the k-loop's tail
+  int it2 = it1, q2 = q1;
+  bool more2 = more1;
 
   f32x16 acc[MI][NJ];
 #pragma unroll
@@ -803,40 +889,131 @@ conv_hc32_kernel(const uint16_t* __restrict__ src,
 
   const uint32_t wrow = (uint32_t)((wn * NJ * 32 + l31) * RB +
                                    16 * (lh ^ ((l31 >> 3) & 1)));
+  // ABL 128: the hand-over stamps (see above)
+  unsigned long long st_bar = 0, st_sum[4] = {0, 0, 0, 0};
+  unsigned st_n = 0, st_ne = 0;
+  bool st_epi = false, st_open = false;
+  auto stamp_bar = [&](bool epi_next) __attribute__((always_inline)) {
+    if constexpr ((ABL & 128) != 0) {
+      const unsigned long long now = __builtin_readcyclecounter();
+      if (st_bar) {
+        st_sum[1] += now - st_bar;
+        ++st_n;
+        if (st_epi) {
+          st_sum[3] += now - st_bar;
+          ++st_ne;
+        }
+      }
+      st_bar = now;
+      st_epi = epi_next;
+      st_open = true;
+    }
+  };
+  auto stamp_mfma = [&](bool landed) __attribute__((always_inline)) {
+    if constexpr ((ABL & 128) != 0) {
+      if (st_open) {   // wave-uniform
+        if (landed) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const unsigned long long now = __builtin_readcyclecounter();
+        st_sum[0] += now - st_bar;
+        if (st_epi) st_sum[2] += now - st_bar;
+        st_open = false;
+      }
+    }
+  };
   int q = 0;
   uint32_t cur = 0;
+  // HO: the k-step-0 fragments of the stage about to run, read at the
+  // hand-over.  The compiler gives them registers of their own (a third
+  // fragment buffer, no copies), which the 128-channel tile does not have:
+  // it reads only the window fragments and NPA of its four weight fragments
+  // ahead, the rest at the top of the k-loop.
+  constexpr int NPA = MI * NJ <= 6 ? NJ : (EMC == 0 ? 0 : 2);
+  constexpr int NPB = NPA > 0 ? MI : 0;
+  bf16x8 pa[NJ], pb[MI];
+  auto rd_ahead = [&](uint32_t st) __attribute__((always_inline)) {
+    const uint32_t wb = st + (uint32_t)g.WIN + wrow;
+#pragma unroll
+    for (int i = 0; i < NPB; ++i)
+      pb[i] = *(lds_bf16x8*)(sm + st + ra[i][0]);
+#pragma unroll
+    for (int j = 0; j < NPA; ++j)
+      pa[j] = *(lds_bf16x8*)(sm + wb + j * 32 * RB);
+  };
+  if constexpr (HO) rd_ahead(0);
   for (;;) {
     const bool last = q == NQ - 1;
     int ptl, gi, nt;
-    decode(item, ptl, gi, nt);
+    if constexpr (HO) {
+      ptl = c_ptl;
+      gi = c_gi;
+      nt = c_nt;
+    } else {
+      decode(item, ptl, gi, nt);
+    }
     const uint32_t p0 = (uint32_t)ptl * TPX;
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
       for (int s = 0; s < T; ++s) asm volatile("" : "+v"(ra[i][s]));
     const uint32_t nxt = cur ^ STAGE;
-    const uint32_t wb = cur + (uint32_t)g.WIN + wrow;
     // the k-steps (taps) of this stage; the next stage's DMA slots spread
-    // over the first ~2/3 of them
-    constexpr int NKSD = (ABL & 2) ? 1 : (ABL & 16) ? T : (2 * T + 2) / 3;
-    auto rd = [&](int s, bf16x8* a, bf16x8* b) __attribute__((always_inline)) {
+    // over the first ~2/3 of them (HO: none at the last k-step, whose
+    // MFMAs follow the stage's DMA wait)
+    constexpr int NKSD = (ABL & 2)    ? 1
+                         : (ABL & 16) ? (HO ? T - 1 : T)
+                                      : (2 * T + 2) / 3;
+    static_assert(!HO || NKSD <= T - 1, "no DMA slot at the last k-step");
+    // HO: the k-step whose tail prepares the stage after (it1, q1)
+    constexpr int KB = NKSD;
+    auto rd_at = [&](uint32_t st, int s, bf16x8* a, bf16x8* b)
+                     __attribute__((always_inline)) {
+      const uint32_t wb = st + (uint32_t)g.WIN + wrow;
 #pragma unroll
       for (int i = 0; i < MI; ++i)
-        b[i] = *(lds_bf16x8*)(sm + cur + ra[i][s]);
+        b[i] = *(lds_bf16x8*)(sm + st + ra[i][s]);
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
         a[j] = *(lds_bf16x8*)(sm + wb + j * 32 * RB + s * 32);
+    };
+    auto rd = [&](int s, bf16x8* a, bf16x8* b) __attribute__((always_inline)) {
+      rd_at(cur, s, a, b);
     };
     // the stage's k-steps, taps in the order R, R + 1, ... (mod T)
     auto kloop = [&](auto rc) __attribute__((always_inline)) {
       constexpr int R = decltype(rc)::value;
       bf16x8 fa[2][NJ], fb[2][MI];
-      rd(R % T, fa[0], fb[0]);
+      if constexpr (HO) {   // on the way since the last hand-over
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+          fb[0][i] = i < NPB ? pb[i] : *(lds_bf16x8*)(sm + cur + ra[i][0]);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          fa[0][j] = j < NPA ? pa[j]
+                             : *(lds_bf16x8*)(sm + cur + (uint32_t)g.WIN +
+                                              wrow + j * 32 * RB);
+      } else {
+        rd(R % T, fa[0], fb[0]);
+      }
 #pragma unroll
       for (int s = 0; s < T; ++s) {
-        if (s + 1 < T)
+        if (s + 1 < T) {
           rd((s + 1 + R) % T, fa[(s + 1) & 1], fb[(s + 1) & 1]);
+        } else if (HO && !last) {   // workgroup-uniform
+          // this wave's reads of cur are done and its pieces of (it1, q1)
+          // landed; past the barrier that holds for every wave, and the
+          // next stage's first fragments are read under this k-step's MFMAs
+          if constexpr ((ABL & 8) == 0)
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+          else
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_s_barrier();
+          asm volatile("" ::: "memory");
+          stamp_bar(false);
+          rd_ahead(nxt);
+          stamp_mfma(false);   // this k-step's fragments have landed
+        }
         __builtin_amdgcn_sched_barrier(0);
+        if (s == 0) stamp_mfma(true);
         if constexpr ((ABL & 4) == 0) {
 #pragma unroll
           for (int i = 0; i < MI; ++i)
@@ -856,15 +1033,30 @@ conv_hc32_kernel(const uint16_t* __restrict__ src,
               if (k * NKSD / NSLOT == s) issue_slot(k, nxt, true);
           }
         }
+        if constexpr (HO) {
+          if (s == KB) {   // the stage's DMA slots are all issued
+            it2 = it1;
+            q2 = q1;
+            next(it2, q2);
+            more2 = it2 < g.items;
+            if (more2) prepare_ho(it2, q2);
+          }
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
     };
     kloop(std::integral_constant<int, 0>{});
+    if constexpr (HO && !WTAIL) {
+      if (more2 && q2 == 0) prepare_lanes();   // wave-uniform
+    }
     // stage (it1, q1) landed; every read of (item, q) done
-    if constexpr ((ABL & 8) == 0)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    if (!HO || last) {
+      if constexpr ((ABL & 8) == 0)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      stamp_bar(last);
+    }
     if (last) {
       // lane: pixel l31 of each m-tile, output channels 16 lh + r of each
       // n-tile (the row permutation): bias, activation, derivative of the
@@ -1042,7 +1234,9 @@ conv_hc32_kernel(const uint16_t* __restrict__ src,
           if constexpr (MI > 3) epi_i(std::integral_constant<int, 3>{});
         }
       };
-      if (!aux && act == ACT_STRICT_RELU)
+      if constexpr (EMC >= 0)   // chosen at the launch (hc32_em)
+        epi(std::integral_constant<int, EMC>{});
+      else if (!aux && act == ACT_STRICT_RELU)
         epi(std::integral_constant<int, 1>{});
       else if (aux && act == ACT_LINEAR && aux_act == ACT_STRICT_RELU && !bias)
         epi(std::integral_constant<int, 2>{});
@@ -1057,15 +1251,39 @@ conv_hc32_kernel(const uint16_t* __restrict__ src,
       if (more1) slots(it1);
       // the staging slots lie in the buffer the next stage's DMA fills
       if constexpr (TS) __builtin_amdgcn_s_barrier();
+      if constexpr (HO) {   // the new item's first fragments (its ra[][])
+        if (more1) rd_ahead(nxt);
+      }
     }
     if (!more1) break;
     item = it1;
     q = q1;
-    next(it1, q1);
-    more1 = it1 < g.items;
-    if (more1) prepare(it1, q1);
+    if constexpr (HO) {
+      if (q == 0) {   // the item prepared last is now in the k-loop
+        c_ptl = n_ptl;
+        c_gi = n_gi;
+        c_nt = n_nt;
+      }
+      it1 = it2;
+      q1 = q2;
+      more1 = more2;
+    } else {
+      next(it1, q1);
+      more1 = it1 < g.items;
+      if (more1) prepare(it1, q1);
+    }
     cur ^= STAGE;
   }
+#ifdef HVK_HC_ABL
+  if constexpr ((ABL & 128) != 0) {
+    if (t == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) atomicAdd(&g_hc_stamps[k], st_sum[k]);
+      atomicAdd(&g_hc_stamps[4], (unsigned long long)st_n);
+      atomicAdd(&g_hc_stamps[5], (unsigned long long)st_ne);
+    }
+  }
+#endif
 }
 
 // Stage-major filter bank of conv_hc32: packed[g][nt][c][n][t][16] holds,
@@ -1149,6 +1367,12 @@ struct HcCand { int var, KH, KW, KHS, WM, WN, NJW, NBW, m32, mi = 2; };
 int g_hc32 = 1;
 int g_hc_last = 0;   // configuration of the last conv_hc launch (tests)
 int g_hc32_ts = 1;   // conv_hc32 epilogue stores staged through LDS
+// conv_hc32 stage hand-over: 1 the barrier under the last k-step's MFMAs and
+// the bookkeeping in the k-loop's tail (default), 0 the round-6 order
+int g_hc32_ho = 1;
+// persistent grid cap (one workgroup per CU; tests lower it so that tiny
+// shapes walk many items per workgroup)
+int g_hc_max_wgs = kCUs;
 // per kernel size, in order of preference (the first whose n-tile divides
 // the group's outputs and whose two stages fit the LDS)
 constexpr HcCand kHcCands[] = {
@@ -1258,8 +1482,10 @@ HcPlan hc_plan(int N, int H, int W, int C, int OH, int OW, int OCT, int KH,
     g.fOHW = make_fastdiv(g.OHW);
     g.fHPd = make_fastdiv(g.HPd);
     g.fWp = make_fastdiv(g.Wp);
+    g.fNT = make_fastdiv(g.NT);
+    g.fG = make_fastdiv(groups);
     p.lds = lds;
-    p.grid = std::min(g.items, kCUs);
+    p.grid = std::min(g.items, g_hc_max_wgs);
     p.var = k.var;
     p.KH = KH;
     p.KW = KW;
@@ -1297,7 +1523,7 @@ long long hc32_wpack_bytes(const HcPlan& p) {
 }
 
 template <int KH, int KW, int WM, int WN, int NJ, int NBW, int ABL = 0,
-          int MI = 2, bool TS = false>
+          int MI = 2, bool TS = false, bool HO = false, int EMC = -1>
 hipError_t go_hc32_ts(const HcPlan& p, const void* src, const void* wts,
                    const float* bias, void* out, const void* aux, int act,
                    int aux_act, hipStream_t s) {
@@ -1311,7 +1537,7 @@ hipError_t go_hc32_ts(const HcPlan& p, const void* src, const void* wts,
                        WN * NJ * 32, p.g.flip, pieces, p.fwd_w);
     wts = p.wpack;
   }
-  auto kern = conv_hc32_kernel<KH, KW, WM, WN, NJ, NBW, ABL, MI, TS>;
+  auto kern = conv_hc32_kernel<KH, KW, WM, WN, NJ, NBW, ABL, MI, TS, HO, EMC>;
   static bool attr = false;   // once per instantiation, before any capture
   if (!attr) {
     hipError_t e = hipFuncSetAttribute(
@@ -1326,15 +1552,39 @@ hipError_t go_hc32_ts(const HcPlan& p, const void* src, const void* wts,
   return launch_status(s);
 }
 
+// EM of conv_hc32_kernel's epilogue for a launch's arguments (the ladder the
+// EMC = -1 kernel walks on the device)
+int hc32_em(const float* bias, const void* aux, int act, int aux_act) {
+  if (!aux && act == ACT_STRICT_RELU) return 1;
+  if (aux && act == ACT_LINEAR && aux_act == ACT_STRICT_RELU && !bias)
+    return 2;
+  return 0;
+}
+
 template <int KH, int KW, int WM, int WN, int NJ, int NBW, int ABL = 0>
 hipError_t go_hc32(const HcPlan& p, const void* src, const void* wts,
                    const float* bias, void* out, const void* aux, int act,
                    int aux_act, hipStream_t s) {
-  if (p.g.ts)
-    return go_hc32_ts<KH, KW, WM, WN, NJ, NBW, ABL, 2, true>(
-        p, src, wts, bias, out, aux, act, aux_act, s);
-  return go_hc32_ts<KH, KW, WM, WN, NJ, NBW, ABL, 2, false>(
-      p, src, wts, bias, out, aux, act, aux_act, s);
+#define HC32_TS(TSV, HOV, EMV) \
+  return go_hc32_ts<KH, KW, WM, WN, NJ, NBW, ABL, 2, TSV, HOV, EMV>(          \
+      p, src, wts, bias, out, aux, act, aux_act, s)
+  // the new hand-over: the production kernel (and the stamp build, ABL 128);
+  // the other diagnostic instantiations keep the round-6 order
+  if (g_hc32_ho && (ABL & ~128) == 0) {
+    // the epilogue of this launch (conv_hc32_kernel's EM); staged stores
+    // exist only for backward-data, which never takes EM 1
+    const int em = hc32_em(bias, aux, act, aux_act);
+    if (p.g.ts) {
+      if (em == 2) HC32_TS(true, true, 2);
+      HC32_TS(true, true, 0);
+    }
+    if (em == 1) HC32_TS(false, true, 1);
+    if (em == 2) HC32_TS(false, true, 2);
+    HC32_TS(false, true, 0);
+  }
+  if (p.g.ts) HC32_TS(true, false, -1);
+  HC32_TS(false, false, -1);
+#undef HC32_TS
 }
 
 #ifdef HVK_HC_ABL
@@ -1347,7 +1597,7 @@ hipError_t go_hc32_abl(const HcPlan& p, const void* src, const void* wts,
     case A: return go_hc32<KH, KW, WM, WN, NJ, NBW, A>(                       \
         p, src, wts, bias, out, aux, act, aux_act, s);
     HC32_ABL(1) HC32_ABL(2) HC32_ABL(4) HC32_ABL(8) HC32_ABL(16) HC32_ABL(32)
-    HC32_ABL(9) HC32_ABL(64)
+    HC32_ABL(9) HC32_ABL(64) HC32_ABL(128)
 #undef HC32_ABL
     default: return go_hc32<KH, KW, WM, WN, NJ, NBW, 0>(
         p, src, wts, bias, out, aux, act, aux_act, s);
@@ -1435,6 +1685,18 @@ HVK_API void hvk_hc_variant(int v) { g_hc_variant = v; }
 // Diagnostic ablation builds of configurations 5, 6 and 7 (see conv_hc_kernel's
 // ABL); 0 = the production kernel.
 HVK_API void hvk_hc_ablation(int a) { g_hc_abl = a; }
+#ifdef HVK_HC_ABL
+// conv_hc32's hand-over stamps (ABL 128) summed since the last call: out[0-3]
+// clock ticks {barrier -> first MFMA, barrier -> next barrier, the same two
+// after an epilogue}, out[4-5] the stages counted; synchronises the device
+HVK_API int hvk_hc_stamps(unsigned long long* out) {
+  unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_hc_stamps), sizeof(z));
+  if (e == hipSuccess)
+    e = hipMemcpyToSymbol(HIP_SYMBOL(g_hc_stamps), z, sizeof(z));
+  return (int)e;
+}
+#endif
 // window row pitch pad (8 default; see g_hc_pad)
 HVK_API void hvk_hc_pitch_pad(int p) { g_hc_pad = p; }
 // conv_hc32 candidates (32x32x16 MFMA, one tap per k-step): 1 on (default),
@@ -1442,6 +1704,14 @@ HVK_API void hvk_hc_pitch_pad(int p) { g_hc_pad = p; }
 HVK_API void hvk_hc32(int on) { g_hc32 = on; }
 // conv_hc32 epilogue stores: 1 staged through LDS (default), 0 direct
 HVK_API void hvk_hc32_ts(int on) { g_hc32_ts = on; }
+// conv_hc32 stage hand-over: 1 the new order (default), 0 the round-6 order
+// (A/B runs and tests; the results are bit-identical)
+HVK_API void hvk_hc32_handover(int on) { g_hc32_ho = on; }
+// workgroups of the persistent conv_hc grids at most (default 256, one per
+// CU; clamped to 1 .. 256)
+HVK_API void hvk_hc_max_wgs(int n) {
+  g_hc_max_wgs = std::min(std::max(n, 1), kCUs);
+}
 // configuration (kHcCands var) of the last hvk_conv_{fwd,dgrad}_hc launch
 HVK_API int hvk_hc_last_variant() { return g_hc_last; }
 

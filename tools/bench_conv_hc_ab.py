@@ -2,8 +2,10 @@
 against the kernels they replace (ops.set_conv_hc(False): T4 / 256x256
 ping-pong / 128-row implicit GEMM / conv_halo), interleaved round by round
 in ONE process on random operands; median TF/s at the logical
-2 N OH OW OC KH KW C/g FLOPs.  Extra settings "hcV" force conv_hc.hip
-configuration V.
+2 N OH OW OC KH KW C/g FLOPs.  "ho0" is "hc" with conv_hc32's round-6 stage
+hand-over (ops.set_conv_hc32_handover(False)); the line also gives the
+median and the minimum ms of both orders.  Extra settings "hcV" force
+conv_hc.hip configuration V.
 
     python tools/bench_conv_hc_ab.py [alexnet_batch] [rounds] [vgg_batch]
                                      [variants, e.g. 2,3]
@@ -84,30 +86,42 @@ def main():
                                          1, 1))]
     # hc: the automatic policy (conv_hc32 where it applies); hc16: the same
     # with the 32x32x16 configurations off; base: no halo conv at all
-    settings = [("hc", True, -2, True), ("hc16", True, -2, False),
-                ("base", False, -2, True)] + \
-        [("hc%d" % v, True, v, True) for v in variants]
+    settings = [("hc", True, -2, True, True), ("ho0", True, -2, True, False),
+                ("hc16", True, -2, False, True),
+                ("base", False, -2, True, True)] + \
+        [("hc%d" % v, True, v, True, True) for v in variants]
     out = {}
     for name, shp in cases:
         fl, fn = case(*shp)
-        res = {k: [] for k, _, _, _ in settings}
+        res = {s[0]: [] for s in settings}
         taken = {}
-        for _ in range(rounds):
-            for key, on, var, m32 in settings:
-                ops.set_conv_hc(on, var)
-                ops.set_conv_hc32(m32)
-                res[key].append(fl / timeit(fn) / 1e12)
-                taken[key] = ops.conv_hc_last_variant() if on else 0
-        ops.set_conv_hc(True, -2)
-        ops.set_conv_hc32(True)
+        try:
+            for _ in range(rounds):
+                for key, on, var, m32, ho in settings:
+                    ops.set_conv_hc(on, var)
+                    ops.set_conv_hc32(m32)
+                    ops.set_conv_hc32_handover(ho)
+                    res[key].append(fl / timeit(fn) / 1e12)
+                    taken[key] = ops.conv_hc_last_variant() if on else 0
+        finally:
+            ops.set_conv_hc(True, -2)
+            ops.set_conv_hc32(True)
+            ops.set_conv_hc32_handover(True)
         med = {k: statistics.median(v) for k, v in res.items()}
+        # ms per launch of the two hand-over orders: median, min, max
+        ms = {k: [fl / (tf * 1e12) * 1e3 for tf in res[k]]
+              for k in ("hc", "ho0")}
         out[name] = {"shape": shp, "tflops": med, "runs": res,
-                     "variant": taken}
+                     "variant": taken, "ms": ms}
         print("%-18s " % name + "  ".join(
-            "%s %7.1f TF" % (k, med[k]) for k, _, _, _ in settings) +
-            "  (hc/hc16 %.2fx, hc/base %.2fx; hc var %d)" % (
+            "%s %7.1f TF" % (s[0], med[s[0]]) for s in settings) +
+            "  (hc/hc16 %.2fx, hc/base %.2fx, hc/ho0 %.3fx; hc var %d)" % (
                 med["hc"] / med["hc16"], med["hc"] / med["base"],
-                taken["hc"]), flush=True)
+                med["hc"] / med["ho0"], taken["hc"]) +
+            "  ms med/min/max " + ", ".join(
+                "%s %.4f/%.4f/%.4f" % (k, statistics.median(v), min(v),
+                                       max(v)) for k, v in ms.items()),
+            flush=True)
         del fn
         torch.cuda.empty_cache()
     os.makedirs("gpurun_out", exist_ok=True)

@@ -23,7 +23,8 @@ for p in "ABL":
     if not f:
         continue
     for r in csv.DictReader(open(f[0])):
-        k = r["Kernel_Name"].split("(")[0].replace("void ", "")[:70]
+        k = r["Kernel_Name"].replace("void ", "").replace(
+            "(anonymous namespace)::", "").split("(")[0][:70]
         agg[k][r["Counter_Name"]] += float(r["Counter_Value"])
         if p == "B":
             ns[k].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))

@@ -813,6 +813,21 @@ def set_conv_hc32(on):
         _lib.lib().hvk_hc32(int(bool(on)))
 
 
+def set_conv_hc32_handover(on):
+    """A/B knob of conv_hc32's stage hand-over (default on: the stage barrier
+    under the last k-step's MFMAs, the next stage's bookkeeping in the
+    k-loop's tail); off is the round-6 order.  Results are bit-identical."""
+    if _lib.available():
+        _lib.lib().hvk_hc32_handover(int(bool(on)))
+
+
+def set_conv_hc_max_wgs(n=256):
+    """Cap of the persistent conv_hc grids (default 256, one workgroup per
+    CU); tests lower it so that tiny shapes walk many items per workgroup."""
+    if _lib.available():
+        _lib.lib().hvk_hc_max_wgs(int(n))
+
+
 def conv_hc_last_variant():
     """conv_hc.hip configuration of the last halo conv launch (tests)."""
     return int(_lib.lib().hvk_hc_last_variant())

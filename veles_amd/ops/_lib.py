@@ -129,7 +129,14 @@ _SIGS = {
     "hvk_end_stream_capture": [P],
     "hvk_stream_create": [],
 }
-_OPTIONAL = {}
+# setters an older library loaded through HVK_LIBRARY for a whole-step A/B
+# run (tools/gpu_bench_ab.sh) may lack; only tests and tools call them
+_OPTIONAL = {
+    "hvk_hc32_handover": [I],
+    "hvk_hc_max_wgs": [I],
+    # only in the -DHVK_HC_ABL build (tools/build_abl.py hc)
+    "hvk_hc_stamps": [P],
+}
 # functions returning a pointer / a 64-bit int (every other one returns int)
 _PTR_RET = {"hvk_stream_create"}
 _LL_RET = {"hvk_conv_wgrad_halo", "hvk_conv_wgrad_halo_fp8",
@@ -153,6 +160,11 @@ def _load():
             fn.argtypes = sig
             fn.restype = ctypes.c_void_p if name in _PTR_RET else \
                 ctypes.c_longlong if name in _LL_RET else ctypes.c_int
+        for name, sig in _OPTIONAL.items():
+            fn = getattr(lib, name, None)
+            if fn is not None:
+                fn.argtypes = sig
+                fn.restype = ctypes.c_int
         # A/B schedule selectors for whole-run experiments (bench.py under
         # an environment setting; tests and tools call the setters directly)
         for env, fn in (("VELES_AMD_GEMM_VARIANT", "hvk_set_gemm_variant"),
