@@ -29,7 +29,8 @@ __all__ = ["ACT", "gemm", "linear_fwd", "conv_out_size", "conv_fwd",
            "act_bwd", "pool_fwd", "pool_bwd", "lrn_fwd", "lrn_bwd",
            "softmax_ce", "mse", "sgd_update", "dropout", "xorshift1024star",
            "xorshift128plus", "join", "cast", "fill_minibatch",
-           "mean_disp_normalize", "act_code"]
+           "mean_disp_normalize", "act_code", "kohonen_coords",
+           "kohonen_argmin", "kohonen_update"]
 
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2, torch.int32: 3,
       torch.float16: 4}
@@ -2348,3 +2349,156 @@ def mean_disp_normalize(x, mean, rdisp, out=None, out_dtype=None):
         rdisp.reshape(1, -1).float()
     out.copy_(v.reshape(out.shape).to(out.dtype))
     return out
+
+
+# ------------------------------------------------------------- Kohonen maps
+# docs/OPS.md "Kohonen maps"; kernels in csrc/kernels/kohonen.hip.
+_KOH_TILE = 128          # neurons per tile of both kernels
+_KOH_XTILE = 64          # samples (winner search) / features (update) per tile
+_KOH_KTILE = 32          # batch rows per K tile of the update
+_KOH_WGS = 512           # workgroups wanted before a kernel stops splitting
+_KOH_WS_MAX = 1 << 26    # floats: cap of the update's slice workspace
+
+
+def kohonen_coords(sx, sy, device="cpu"):
+    """Grid positions float32 [sx * sy][2] of a rectangular map: neuron
+    n = y * sx + x sits at ((x - (sx-1)/2) h, (y - (sy-1)/2) h) with
+    h = 2 / max(sx-1, sy-1, 1), so the long side spans [-1, 1]."""
+    sx, sy = int(sx), int(sy)
+    if sx < 1 or sy < 1:
+        raise ValueError("kohonen_coords: shape (%d, %d)" % (sx, sy))
+    h = 2.0 / max(sx - 1, sy - 1, 1)
+    gx = (torch.arange(sx, dtype=torch.float64) - (sx - 1) / 2.0) * h
+    gy = (torch.arange(sy, dtype=torch.float64) - (sy - 1) / 2.0) * h
+    c = torch.stack([gx.repeat(sy), gy.repeat_interleave(sx)], 1)
+    return c.to(torch.float32).to(device)
+
+
+def _kohonen_args(name, x, w, n):
+    """Shared host checks; returns (x as [rows][D], rows used, NN, D)."""
+    if w.dtype != torch.float32 or w.dim() != 2:
+        raise ValueError("%s: weights must be float32 [NN][D], got %s %s" %
+                         (name, w.dtype, tuple(w.shape)))
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("%s: input must be float32 or bfloat16, got %s" %
+                         (name, x.dtype))
+    if x.dim() < 1 or x.shape[0] < 1:
+        raise ValueError("%s: empty input %s" % (name, tuple(x.shape)))
+    if not x.is_contiguous() or not w.is_contiguous():
+        raise ValueError("%s: input and weights must be contiguous" % name)
+    if x.device != w.device:
+        raise ValueError("%s: input on %s, weights on %s" %
+                         (name, x.device, w.device))
+    NN, D = w.shape
+    x2 = x.view(x.shape[0], -1)
+    if NN < 1 or D < 1 or x2.shape[1] != D:
+        raise ValueError("%s: input %s does not match weights %s" %
+                         (name, tuple(x.shape), tuple(w.shape)))
+    n = x2.shape[0] if n is None else int(n)
+    if n < 1 or n > x2.shape[0]:
+        raise ValueError("%s: %d valid rows of %d" % (name, n, x2.shape[0]))
+    if n * D >= 1 << 31 or NN * D >= 1 << 31:
+        raise ValueError("%s: %d x %d input / %d x %d weights exceed 2^31 "
+                         "elements" % (name, n, D, NN, D))
+    return x2, n, NN, D
+
+
+def _kohonen_out(name, what, t, dtype, size, device):
+    if t is None:
+        return None
+    if t.dtype != dtype or t.dim() != 1 or t.shape[0] < size or \
+            not t.is_contiguous() or t.device != device:
+        raise ValueError("%s: %s must be a contiguous %s [>= %d] on %s" %
+                         (name, what, dtype, size, device))
+    return t
+
+
+def _kohonen_fn(name):
+    fn = getattr(_lib.lib(), name, None)
+    if fn is None:
+        raise _lib.KernelLibraryMissing(
+            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
+            (_lib.LIB_PATH, name))
+    return fn
+
+
+def kohonen_argmin(x, w, n=None, argmin=None, qerr=None, winners=None,
+                   splits=0):
+    """Winners of the first ``n`` rows of ``x`` on the map ``w`` (float32
+    [NN][D]): argmin[b] = argmin_n (|w[n]|^2 - 2 x[b].w[n]), ties to the
+    lowest n.  ``qerr`` (float32) receives max(0, |x[b]|^2 + that minimum),
+    ``winners`` (int32 [NN]) is incremented at every winner.  ``splits``
+    forces the number of neuron slices on the GPU (0: chosen).  Returns the
+    int32 winners, a view of ``argmin`` when that is given."""
+    name = "kohonen_argmin"
+    x2, n, NN, D = _kohonen_args(name, x, w, n)
+    dev = w.device
+    if argmin is None:
+        argmin = torch.empty(n, dtype=torch.int32, device=dev)
+    _kohonen_out(name, "argmin", argmin, torch.int32, n, dev)
+    _kohonen_out(name, "qerr", qerr, torch.float32, n, dev)
+    _kohonen_out(name, "winners", winners, torch.int32, NN, dev)
+    splits = int(splits)
+    if splits < 0:
+        raise ValueError("%s: splits %d" % (name, splits))
+    if _gpu(w):
+        tb = -(-n // _KOH_XTILE)
+        nt = -(-NN // _KOH_TILE)
+        sp = max(1, min(splits or _KOH_WGS // tb, nt))
+        ws = _grow_ws("kohonen_argmin", (2 * sp + 1) * n, torch.float32, dev)
+        _lib.check(_kohonen_fn("hvk_kohonen_argmin")(
+            _p(x2), DT[x2.dtype], _p(w), n, NN, D, D, _p(argmin), _p(qerr),
+            _p(winners), _p(ws), sp, _s(w)), "hvk_kohonen_argmin")
+        return argmin[:n]
+    xs = x2[:n].float()
+    s = (w * w).sum(1).unsqueeze(0) - 2.0 * (xs @ w.t())
+    a = s.argmin(1)      # the first of equal minima
+    argmin[:n] = a.to(torch.int32)
+    if qerr is not None:
+        v = s.gather(1, a.unsqueeze(1)).squeeze(1)
+        qerr[:n] = ((xs * xs).sum(1) + v).clamp_(min=0)
+    if winners is not None:
+        winners[:NN] += torch.bincount(a, minlength=NN).to(torch.int32)
+    return argmin[:n]
+
+
+def kohonen_update(x, w, coords, argmin, sigma, gradient, n=None, splits=0):
+    """One neighbourhood step on ``w`` in place, over the first ``n`` rows:
+    w[m] += (gradient / n) * sum_b G[b][m] (x[b] - w[m]) with G[b][m] =
+    exp(-|coords[m] - coords[argmin[b]]|^2 / (2 sigma^2)).  Indices outside
+    the map are clamped into it.  ``splits`` forces the number of batch
+    slices on the GPU (0: chosen)."""
+    name = "kohonen_update"
+    x2, n, NN, D = _kohonen_args(name, x, w, n)
+    dev = w.device
+    if coords.dtype != torch.float32 or tuple(coords.shape) != (NN, 2) or \
+            not coords.is_contiguous() or coords.device != dev:
+        raise ValueError("%s: coords must be a contiguous float32 [%d][2] on "
+                         "%s" % (name, NN, dev))
+    _kohonen_out(name, "argmin", argmin, torch.int32, n, dev)
+    sigma, gradient, splits = float(sigma), float(gradient), int(splits)
+    if not sigma > 0 or splits < 0:
+        raise ValueError("%s: sigma %r, splits %d" % (name, sigma, splits))
+    inv2s2 = 1.0 / (2.0 * sigma * sigma)
+    if _gpu(w):
+        tiles = -(-NN // _KOH_TILE) * -(-D // _KOH_XTILE)
+        nk = -(-n // _KOH_KTILE)
+        sp = splits
+        if not sp:
+            sp = min(_KOH_WGS // tiles, nk // 4)
+            while sp > 1 and sp * NN * (D + 1) > _KOH_WS_MAX:
+                sp //= 2
+        sp = max(1, min(sp, nk))
+        ws = None if sp == 1 else _grow_ws(
+            "kohonen_update", sp * NN * (D + 1), torch.float32, dev)
+        _lib.check(_kohonen_fn("hvk_kohonen_update")(
+            _p(x2), DT[x2.dtype], _p(w), _p(coords), _p(argmin), n, NN, D, D,
+            inv2s2, gradient / n, _p(ws), sp, _s(w)), "hvk_kohonen_update")
+        return w
+    xs = x2[:n].float()
+    a = argmin[:n].long().clamp_(0, NN - 1)
+    d = coords.unsqueeze(1) - coords.unsqueeze(0)
+    K = torch.exp(-(d * d).sum(2) * inv2s2)
+    G = K[a]                                   # [n][NN]
+    w += (gradient / n) * (G.t() @ xs - G.sum(0).unsqueeze(1) * w)
+    return w

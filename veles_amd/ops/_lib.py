@@ -136,6 +136,11 @@ _OPTIONAL = {
     "hvk_hc_max_wgs": [I],
     # only in the -DHVK_HC_ABL build (tools/build_abl.py hc)
     "hvk_hc_stamps": [P],
+    # Kohonen maps (csrc/kernels/kohonen.hip): (X, x_dt, W, B, NN, D, ldx,
+    # argmin, qerr, winners, ws, splits, s) and (X, x_dt, W, coords, argmin,
+    # B, NN, D, ldx, inv2sigma2, gmult, ws, splits, s)
+    "hvk_kohonen_argmin": [P, I, P, I, I, I, I, P, P, P, P, I, P],
+    "hvk_kohonen_update": [P, I, P, P, P, I, I, I, I, F, F, P, I, P],
 }
 # functions returning a pointer / a 64-bit int (every other one returns int)
 _PTR_RET = {"hvk_stream_create"}

@@ -324,3 +324,103 @@ def similarity_order(rows):
         order.append(k)
         used[k] = True
     return numpy.asarray(order)
+
+
+# ------------------------------------------------------------- Kohonen maps
+__all__ += ["KohonenHits", "KohonenNeighborMap", "KohonenInputMaps"]
+
+
+class _KohonenGrid(Plotter):
+    """Base of the Kohonen map plotters: ``shape`` = (sx, sy), neuron
+    n = y * sx + x is cell (row y, column x)."""
+    hide_from_registry = True
+
+    def __init__(self, workflow, **kwargs):
+        super().__init__(workflow, **kwargs)
+        shape = kwargs.get("shape", (8, 8))
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.demand("input")
+
+    def _weights(self):
+        sx, sy = self.shape
+        w = numpy.asarray(to_numpy(self.input), dtype=numpy.float64)
+        return w.reshape(sy, sx, -1)
+
+
+class KohonenHits(_KohonenGrid):
+    """Winner counts per cell (``input``: the winners histogram [NN])."""
+    MAPPING = "kohonen_hits"
+
+    def collect(self):
+        sx, sy = self.shape
+        v = to_numpy(self.input)
+        self.hits_ = numpy.zeros((sy, sx)) if v is None else \
+            numpy.asarray(v, dtype=numpy.float64).reshape(sy, sx)
+
+    def draw(self, fig):
+        ax = fig.add_subplot(111)
+        im = ax.imshow(self.hits_, cmap="viridis")
+        fig.colorbar(im)
+        ax.set_title("hits")
+        if self.hits_.size <= 400:
+            for (i, j), v in numpy.ndenumerate(self.hits_):
+                ax.text(j, i, "%d" % v, ha="center", va="center", fontsize=6,
+                        color="w")
+
+
+class KohonenNeighborMap(_KohonenGrid):
+    """U-matrix: per cell the mean weight distance to its 4-neighbours
+    (``input``: the weights [NN][D])."""
+    MAPPING = "kohonen_neighbor_map"
+
+    @staticmethod
+    def u_matrix(w):
+        """w: [sy][sx][D] -> [sy][sx] mean distance to the 4-neighbours."""
+        sy, sx = w.shape[:2]
+        tot = numpy.zeros((sy, sx))
+        cnt = numpy.zeros((sy, sx))
+        if sy > 1:
+            d = numpy.linalg.norm(w[1:] - w[:-1], axis=2)
+            tot[1:] += d
+            tot[:-1] += d
+            cnt[1:] += 1
+            cnt[:-1] += 1
+        if sx > 1:
+            d = numpy.linalg.norm(w[:, 1:] - w[:, :-1], axis=2)
+            tot[:, 1:] += d
+            tot[:, :-1] += d
+            cnt[:, 1:] += 1
+            cnt[:, :-1] += 1
+        return tot / numpy.maximum(cnt, 1)
+
+    def collect(self):
+        self.umatrix_ = self.u_matrix(self._weights())
+
+    def draw(self, fig):
+        ax = fig.add_subplot(111)
+        im = ax.imshow(self.umatrix_, cmap="bone_r")
+        fig.colorbar(im)
+        ax.set_title("neighbor weight distances")
+
+
+class KohonenInputMaps(_KohonenGrid):
+    """One weight plane per input feature (``input``: the weights; the
+    first ``limit`` features)."""
+    MAPPING = "kohonen_input_maps"
+
+    def __init__(self, workflow, **kwargs):
+        super().__init__(workflow, **kwargs)
+        self.limit = int(kwargs.get("limit", 16))
+
+    def collect(self):
+        self.planes_ = numpy.moveaxis(self._weights(), 2, 0)[:self.limit]
+
+    def draw(self, fig):
+        n = len(self.planes_)
+        cols = int(numpy.ceil(numpy.sqrt(n)))
+        rows = int(numpy.ceil(n / max(cols, 1)))
+        for i in range(n):
+            ax = fig.add_subplot(rows, cols, i + 1)
+            ax.imshow(self.planes_[i], cmap="coolwarm")
+            ax.set_title("input %d" % i, fontsize=7)
+            ax.axis("off")
