@@ -106,7 +106,27 @@ __device__ __forceinline__ bf16x8 tr_read(lds_u8* sm, uint32_t o0,
 // Wp + ow - ow0 from the step's first pixel - the same "pixel base + tap
 // offset" read with the tap row pitch SEGP instead of Wp.  kspan counts
 // steps then, pixels otherwise.
-template <int MT, int NP, int KHT, int KW, int NJW, int PB, bool SEG>
+// LEAN (hvk_halo_lean, default on; off is the loop as it was, kept for A/B
+// and the bitwise tests): the step's address arithmetic without divisions,
+// 64-bit multiply-adds or exec-masked regions.  The non-MFMA instruction
+// stream of the 64-pixel step, not HBM, LDS or the MFMA pipe, bounds this
+// loop (docs/OPS.md "Halo weight-gradient ablation"), and nearly all of it
+// was per-lane work on values that are either invariant per lane or
+// wave-uniform and advancing by a constant:
+//   * DMA offsets are a per-lane invariant (piece row * rowbytes + column
+//     bytes) plus a wave-uniform row base that lean_advance() carries by
+//     adds;
+//     the row / image validity is a range test against scalar bounds;
+//   * the dY offset is a scalar advancing by 64 * OC * 2, and the row
+//     limit is tested only on the step that has one (plim < 64);
+//   * pixel q + 16 i = a_i * OW + b_i of a step starting at column ow0 is
+//     in row a_i + (b_i >= OW - ow0): the window slot of the B fragments is
+//     a lane constant plus a select, not a division per pixel and step;
+//   * the segment form splits slot j = aj * Wp + bj the same way.
+// Barriers, waits, the pixel-to-k mapping and the MFMA order are those of
+// the old loop: results are bit-identical.
+template <int MT, int NP, int KHT, int KW, int NJW, int PB, bool SEG,
+          bool LEAN>
 __global__ void __launch_bounds__(256, 2)
 wgrad_halo_kernel(const uint16_t* __restrict__ x,
                   const uint16_t* __restrict__ dy, float* __restrict__ ws,
@@ -308,14 +328,190 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
     }
   };
 
+  // ---- LEAN: lane invariants and the carried wave-uniform step state
+  // window piece i: l_rs its row term (full-row: window row rs; SEG: kh +
+  // aj), a row no range test accepts where the piece's lane loads nothing;
+  // l_inv its byte offset less the step's scalar base; l_bj (SEG) bj
+  constexpr int kNoRow = 0x40000000;
+  int l_rs[NBW], l_bj[NBW];
+  uint32_t l_inv[NBW];
+  // pixel q + 16 i = a_i * OW + b_i: l_b = b_i, l_k = the stage byte of
+  // window slot a_i * Wp + b_i (+ this lane's trp * 8)
+  int l_b[4];
+  uint32_t l_k[4];
+  const uint32_t wp32 = (uint32_t)g.Wp * 32u;
+  if constexpr (LEAN) {
+#pragma unroll
+    for (int i = 0; i < NBW; ++i) {
+      if constexpr (SEG) {
+        const uint32_t aj = fdiv((uint32_t)b_j[i], g.fWp);
+        const int bj = b_j[i] - (int)aj * g.Wp;
+        const int r = b_rs[i] + (int)aj;
+        l_bj[i] = bj;
+        l_rs[i] = b_ok[i] ? r : kNoRow;
+        l_inv[i] = (uint32_t)r * rowbytes + (uint32_t)(bj - g.pl) * pixbytes +
+                   b_col[i];
+      } else {
+        l_bj[i] = 0;
+        l_rs[i] = b_ok[i] ? b_rs[i] : kNoRow;
+        l_inv[i] = (uint32_t)b_rs[i] * rowbytes + b_col[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t c = (uint32_t)(q + 16 * i);
+      const uint32_t a = fdiv(c, g.fOW);
+      const uint32_t b = c - a * (uint32_t)g.OW;
+      l_b[i] = (int)b;
+      l_k[i] = (a * (uint32_t)g.Wp + b) * 32u + (uint32_t)(trp * 8 + ABYTES);
+    }
+  }
+  // a step's scalars.  base: byte offset of input row oh + kh0 - pt of image
+  // n (SEG: and column ow), modulo 2^32 (the row may be a padding row above
+  // the tensor; a lane that loads has an exact offset below 2^31).  pa:
+  // byte offset of the step's first dY row; plim: valid dY rows.
+  struct LeanStep {
+    uint32_t n, pin, oh, ow, base, pa;
+    int plim;
+  };
+  const uint32_t q64 = fdiv(64u, g.fOW), r64 = 64u - q64 * (uint32_t)g.OW;
+  const uint32_t inc64 = q64 * rowbytes + (SEG ? r64 * pixbytes : 0u);
+  const uint32_t inc_row = rowbytes - (SEG ? (uint32_t)g.OW * pixbytes : 0u);
+  const uint32_t inc_img = (uint32_t)(g.H - g.OH) * rowbytes;
+  const uint32_t astep = 64u * (uint32_t)g.OC * 2u;
+  // the second image's rows: base + b_delta, row slots [rc + b_lo, rc +
+  // b_lo + b_len)
+  const uint32_t b_delta = (uint32_t)(g.H - g.OH - KHT + 1) * rowbytes;
+  const int b_lo = max(0, g.pt - kh0);
+  const int b_len = max(0, g.H + g.pt - kh0 - b_lo);
+  // this wave's window pieces (only the last slot can be past them)
+  const int nb_live = (NB - w + 3) >> 2;
+  auto lean_first = [&]() {
+    LeanStep s;
+    s.n = n0; s.pin = pin0; s.oh = oh0; s.ow = ow0;
+    s.base = (n0 * (uint32_t)g.H + oh0 + (uint32_t)(kh0 - g.pt)) * rowbytes +
+             (SEG ? ow0 * pixbytes : 0u);
+    const uint32_t p = n0 * (uint32_t)g.OHW + pin0;
+    s.pa = p * (uint32_t)g.OC * 2u;
+    s.plim = SEG ? g.OHW - (int)pin0 : pend - (int)p;
+    return s;
+  };
+  auto lean_issue = [&](const LeanStep& s, uint8_t* st) {
+    if constexpr ((HVK_HALO_ABL & 1) != 0) return;
+    if (s.plim >= 64) {   // wave-uniform: every dY row of the step is valid
+#pragma unroll
+      for (int i = 0; i < NAW; ++i)
+        dma16(ra, st + (w * NAW + i) * 1024, s.pa + a_off[i]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NAW; ++i) {
+        const uint32_t v = (a_row[i] < s.plim) ? s.pa + a_off[i] : kBufOOB;
+        dma16(ra, st + (w * NAW + i) * 1024, v);
+      }
+    }
+    if constexpr (SEG) {
+      // slot j = aj * Wp + bj at step column ow: bj + ow < 2 Wp, so one
+      // compare finds its row aj (+ 1) and column bj + ow (- Wp)
+      const int ihb = (int)s.oh + kh0 - g.pt;
+      const uint32_t cw = (uint32_t)max(0, min(g.W, g.OW + g.KW - 1 - g.pl));
+      const uint32_t wrapb = rowbytes - (uint32_t)g.Wp * pixbytes;
+#pragma unroll
+      for (int i = 0; i < NBW; ++i) {
+        bool live = true;
+        if (i == NBW - 1 && NB % 4 != 0) {
+          int nb = nb_live;
+          asm volatile("" : "+s"(nb));
+          live = i < nb;   // wave-uniform
+        }
+        if (live) {
+          const int t = l_bj[i] + (int)s.ow;
+          const bool c = t >= g.Wp;
+          const uint32_t iw = (uint32_t)(t - (c ? g.Wp + g.pl : g.pl));
+          const uint32_t ih = (uint32_t)(l_rs[i] + ihb + (c ? 1 : 0));
+          uint32_t a = l_inv[i] + s.base + (c ? wrapb : 0u);
+          // (pinned, and no short circuit: else hipcc sinks the offset into
+          // an exec-masked region per piece)
+          asm("" : "+v"(a));
+          const bool ok = (iw < cw) & (ih < (uint32_t)g.H);
+          const uint32_t v = ok ? a : kBufOOB;
+          dma16(rb, st + ABYTES + (w + 4 * i) * 1024, v);
+        }
+      }
+      return;
+    }
+    // row slots [a_lo, a_lo + a_len) are image n's, [rc + b_lo, ... + b_len)
+    // image n + 1's
+    const int rc = g.OH - (int)s.oh + KHT - 1;
+    const int ih_a = (int)s.oh + kh0 - g.pt;
+    const int a_lo = max(0, -ih_a);
+    const uint32_t a_len = (uint32_t)max(0, min(rc, g.H - ih_a) - a_lo);
+    const int bl = rc + b_lo;
+    const uint32_t bn = s.n + 1 < (uint32_t)g.N ? (uint32_t)b_len : 0u;
+    const uint32_t base_b = s.base + b_delta;
+#pragma unroll
+    for (int i = 0; i < NBW; ++i) {
+      bool live = true;
+      if (i == NBW - 1 && NB % 4 != 0) {
+        int nb = nb_live;
+        asm volatile("" : "+s"(nb));
+        live = i < nb;   // wave-uniform
+      }
+      if (live) {
+        const int rs = l_rs[i];
+        uint32_t v = (uint32_t)(rs - bl) < bn ? l_inv[i] + base_b : kBufOOB;
+        v = (uint32_t)(rs - a_lo) < a_len ? l_inv[i] + s.base : v;
+        dma16(rb, st + ABYTES + (w + 4 * i) * 1024, v);
+      }
+    }
+  };
+  // the old advance()'s state sequence, by adds: 64 = q64 * OW + r64 and
+  // OH * OW >= 64, so one column carry and one image wrap are enough
+  auto lean_advance = [&](LeanStep& s) {
+    if constexpr (SEG) {
+      s.pin += 64;
+      if (s.pin >= (uint32_t)g.OHW) {   // the next image's first step
+        s.pa += (uint32_t)s.plim * (uint32_t)g.OC * 2u;
+        s.pin = 0; s.oh = 0; s.ow = 0; ++s.n;
+        s.base = (s.n * (uint32_t)g.H + (uint32_t)(kh0 - g.pt)) * rowbytes;
+        s.plim = g.OHW;
+        return;
+      }
+    } else {
+      s.pin += 64;
+      if (s.pin >= (uint32_t)g.OHW) s.pin -= g.OHW;
+    }
+    s.pa += astep;
+    s.plim -= 64;
+    s.oh += q64;
+    s.ow += r64;
+    s.base += inc64;
+    if (s.ow >= (uint32_t)g.OW) {
+      s.ow -= g.OW; ++s.oh; s.base += inc_row;
+    }
+    if (!SEG && s.oh >= (uint32_t)g.OH) {
+      s.oh -= g.OH; ++s.n; s.base += inc_img;
+    }
+  };
+
   const int nk = SEG ? pend - pbeg : (pend - pbeg + 63) >> 6;
-  issue(n0, pin0, oh0, ow0, smem);
+  LeanStep lc{}, ln{};   // the step in the MFMAs, the step being loaded
+  if constexpr (LEAN) {
+    lc = lean_first();
+    lean_issue(lc, smem);
+  } else {
+    issue(n0, pin0, oh0, ow0, smem);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 
   uint32_t nn = n0, pinn = pin0, ohn = oh0, own = ow0;
-  advance(nn, pinn, ohn, own);
+  if constexpr (LEAN) {
+    ln = lc;
+    lean_advance(ln);
+  } else {
+    advance(nn, pinn, ohn, own);
+  }
 
   const bool bwave = bias && kg == 0 && cc == 0 && wc == 0;
 
@@ -324,12 +520,38 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
     constexpr bool WB = decltype(with_bias)::value;
     for (int kt = 0; kt < nk; ++kt) {
       const uint32_t cur = (kt & 1) * STAGE;
-      if (kt + 1 < nk)
-        issue(nn, pinn, ohn, own, smem + ((kt + 1) & 1) * STAGE);
+      if (kt + 1 < nk) {
+        if constexpr (LEAN) lean_issue(ln, smem + ((kt + 1) & 1) * STAGE);
+        else issue(nn, pinn, ohn, own, smem + ((kt + 1) & 1) * STAGE);
+      }
       // B fragment bases (LDS bytes) of this lane's 4 pixels (q + 16 i)
       // for every kh of the tap group
       uint32_t bb[4][KHT];
       const int kp = SEG ? g.SEGP : g.Wp;   // slots per kh
+      if constexpr (LEAN) {
+        // pixel i is in row a_i + (b_i >= OW - ow0) at column ow0 + b_i
+        // (- OW): the carry moves its slot by Wp - OW
+        const int thr = g.OW - (int)lc.ow;
+        const uint32_t dwp = (uint32_t)(g.Wp - g.OW) * 32u;
+        // full-row: slots from row OH - oh0 on are the next image's, KHT - 1
+        // rows further (l_k's trp * 8 < 32 does not move the compare)
+        const uint32_t sb = cur + lc.ow * 32u;
+        const uint32_t wrap = cur + ABYTES + (uint32_t)(g.OH - (int)lc.oh) * wp32;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          uint32_t base = l_k[i] + (l_b[i] >= thr ? dwp : 0u);
+          if constexpr (SEG) {
+            // pixels past the image end read slot 0 (as the old loop)
+            base = q < lc.plim - 16 * i ? base : (uint32_t)(trp * 8 + ABYTES);
+            base += cur;
+          } else {
+            base += sb;
+            base += base >= wrap ? (uint32_t)(KHT - 1) * wp32 : 0u;
+          }
+#pragma unroll
+          for (int kh = 0; kh < KHT; ++kh) bb[i][kh] = base + kh * kp * 32;
+        }
+      } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const uint32_t ow = ow0 + q + 16 * i;
@@ -348,6 +570,7 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
         const uint32_t base = cur + ABYTES + slot * 32 + trp * 8;
 #pragma unroll
         for (int kh = 0; kh < KHT; ++kh) bb[i][kh] = base + kh * kp * 32;
+      }
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
@@ -387,8 +610,13 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      ow0 = own; oh0 = ohn; n0 = nn; pin0 = pinn;
-      advance(nn, pinn, ohn, own);
+      if constexpr (LEAN) {
+        lc = ln;
+        lean_advance(ln);
+      } else {
+        ow0 = own; oh0 = ohn; n0 = nn; pin0 = pinn;
+        advance(nn, pinn, ohn, own);
+      }
     }
   };
   if (wc == 0) {
@@ -825,6 +1053,9 @@ constexpr int kSlots = 512;   // workgroups resident at two per CU
 // +0.1-1.3 % on AlexNet conv2-5, +3.5 % on VGG conv4_2 / conv5_2, results
 // bit-identical (profiles/r6/ab_wgrad_halo_pitch_r6cc.log)
 int g_halo_pad = 2;
+// the bf16 kernel's lean pixel loop (hvk_halo_lean; 0: the old loop, for
+// A/B runs and the bitwise tests)
+int g_halo_lean = 1;
 
 // fp8: 1-byte elements, 128-pixel steps, 16-B slots (Wp = OW + 16) and the
 // fp8 candidate list
@@ -944,10 +1175,14 @@ HVK_API long long hvk_conv_wgrad_halo(const void* X, const void* dY, float* dW,
   const int bias = dbias != nullptr;
   const uint16_t* x = (const uint16_t*)X;
   const uint16_t* dy = (const uint16_t*)dY;
-#define HALO_GO(MT, NP, KHT, KW, NJW, PB, SEG)                                \
-  hipLaunchKernelGGL((wgrad_halo_kernel<MT, NP, KHT, KW, NJW, PB, SEG>), grid, \
-                     blk, 0, s, x, dy, ws, wsb, p.g, p.mtiles, p.cchunks,      \
-                     p.kgroups, p.tiles, p.kspan, bias)
+#define HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, LEAN)                          \
+  hipLaunchKernelGGL(                                                          \
+      (wgrad_halo_kernel<MT, NP, KHT, KW, NJW, PB, SEG, LEAN>), grid, blk, 0,  \
+      s, x, dy, ws, wsb, p.g, p.mtiles, p.cchunks, p.kgroups, p.tiles,         \
+      p.kspan, bias)
+#define HALO_GO(MT, NP, KHT, KW, NJW, PB, SEG)                                 \
+  if (g_halo_lean) HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, true);              \
+  else HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, false)
   switch (p.var) {
     case 1: HALO_GO(128, 2, 3, 3, 9, 7168, false); break;
     case 2: HALO_GO(96, 2, 3, 3, 9, 7168, false); break;
@@ -959,6 +1194,7 @@ HVK_API long long hvk_conv_wgrad_halo(const void* X, const void* dY, float* dW,
     default: return -1;
   }
 #undef HALO_GO
+#undef HALO_GO1
   hipError_t e = launch_status(s);
   if (e != hipSuccess) return (long long)e;
   return finish(ws, wsb, dW, dbias, OC, kk, p.splits, s);
@@ -982,6 +1218,10 @@ static long long finish(float* ws, float* wsb, float* dW, float* dbias, int OC,
 
 // bf16 window row pitch pad (2 default; see g_halo_pad)
 HVK_API void hvk_halo_pitch_pad(int p) { g_halo_pad = p; }
+
+// lean pixel loop of the bf16 halo kernel (1 default; 0: the old loop,
+// bit-identical results)
+HVK_API void hvk_halo_lean(int on) { g_halo_lean = on; }
 
 // the plan's split count (tests / autotune logging)
 HVK_API int hvk_conv_wgrad_halo_splits(int N, int H, int W, int C, int OC,

@@ -4,7 +4,12 @@ the 128-row / T4 GEMM loops (ops.set_halo_wgrad(False)), interleaved round
 by round in ONE process on random operands (cdna_hip_programming.md §5.4
 rules 24-25), reporting the median TF/s per setting.
 
-    python tools/bench_wgrad_ab.py [alexnet_batch] [rounds] [vgg_batch]
+    python tools/bench_wgrad_ab.py [alexnet_batch] [rounds] [vgg_batch] [lean]
+
+With a fourth argument ``lean`` the pair is the halo kernel's lean pixel
+loop against its old loop (ops.set_halo_wgrad_lean(True / False)) instead:
+per layer the median and minimum time of each, and for the layer sum the
+old loop's own round-to-round spread next to the difference.
 
 Writes gpurun_out/bench_wgrad_ab.json."""
 import json
@@ -48,6 +53,7 @@ def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     VB = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+    lean = len(sys.argv) > 4 and sys.argv[4] == "lean"
     cases = [("alex_conv1", (B, 227, 227, 3, 96, 11, 0, 1, 4)),
              ("alex_conv2", (B, 27, 27, 96, 256, 5, 2, 2)),
              ("alex_conv3", (B, 13, 13, 256, 384, 3, 1, 1)),
@@ -60,6 +66,8 @@ def main():
                   ("vgg_conv4_2", (VB, 28, 28, 512, 512, 3, 1, 1)),
                   ("vgg_conv5_2", (VB, 14, 14, 512, 512, 3, 1, 1))]
     out = {}
+    if lean:   # the lean / old pair instead; the same output file
+        out, cases = main_lean(cases, rounds), []
     for name, shp in cases:
         fl, fn = case(*shp)
         res = {"halo": [], "gemm": []}
@@ -78,6 +86,48 @@ def main():
     os.makedirs("gpurun_out", exist_ok=True)
     with open("gpurun_out/bench_wgrad_ab.json", "w") as f:
         json.dump(out, f, indent=1)
+
+
+def main_lean(cases, rounds):
+    """old / lean alternating round by round; times in microseconds"""
+    out = {}
+    sums = {"old": [0.0] * rounds, "lean": [0.0] * rounds}
+    for name, shp in cases:
+        fl, fn = case(*shp)
+        res = {"old": [], "lean": []}
+        try:
+            # one untimed round of both: the first timing of a layer (cold
+            # caches and clocks) would otherwise always be the old loop's
+            for on in (False, True):
+                ops.set_halo_wgrad_lean(on)
+                timeit(fn)
+            for r in range(rounds):
+                for key, on in (("old", False), ("lean", True)):
+                    ops.set_halo_wgrad_lean(on)
+                    t = timeit(fn) * 1e6
+                    res[key].append(t)
+                    sums[key][r] += t
+        finally:
+            ops.set_halo_wgrad_lean(True)
+        st = {k: {"median": statistics.median(v), "min": min(v)}
+              for k, v in res.items()}
+        out[name] = {"shape": shp, "us": st, "runs": res,
+                     "tflops_median": {k: fl / st[k]["median"] / 1e6
+                                       for k in st}}
+        print("%-12s old %8.1f us (min %8.1f)  lean %8.1f us (min %8.1f)  "
+              "%+.1f %%" % (name, st["old"]["median"], st["old"]["min"],
+                            st["lean"]["median"], st["lean"]["min"],
+                            (st["old"]["median"] / st["lean"]["median"] - 1)
+                            * 100), flush=True)
+        del fn
+        torch.cuda.empty_cache()
+    med = {k: statistics.median(v) for k, v in sums.items()}
+    spread = max(sums["old"]) - min(sums["old"])
+    out["sum"] = {"runs": sums, "median": med, "old_spread": spread}
+    print("sum          old %8.1f us  lean %8.1f us  gain %.1f us, the old "
+          "loop's own spread %.1f us" % (med["old"], med["lean"],
+                                         med["old"] - med["lean"], spread))
+    return out
 
 
 if __name__ == "__main__":

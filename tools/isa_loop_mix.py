@@ -1,0 +1,119 @@
+"""Instruction mix of the MFMA-bearing loops of a gfx950 assembly listing.
+
+    hipcc <the flags of veles_amd/ops/build.py> --cuda-device-only -S \
+        csrc/kernels/wgrad_halo.hip -o wgrad_halo.s
+    python tools/isa_loop_mix.py wgrad_halo.s [kernel-name-substring]
+
+For every kernel (whose mangled name holds the substring) it finds the loops
+(a label and a later branch back to it) that hold MFMAs and are inside no
+other such loop, and buckets their instructions by broad class, by mnemonic
+prefix only: MFMA, VALU (and, of those, the quarter-rate integer multiplies
+and 64-bit multiply-adds), SALU, branches, waits, LDS and buffer loads.
+``saveexec`` counts the exec-masked regions opened in the loop.  The counts
+are static (an inner scalar loop counts once).  Needs no GPU.
+"""
+import re
+import sys
+
+QUARTER = ("v_mul_lo", "v_mul_hi", "v_mad_u64", "v_mad_i64")
+COLS = ("mfma", "valu", "quarter", "salu", "branch", "wait", "lds", "buffer",
+        "other", "saveexec")
+
+
+def classify(op):
+    if op.startswith("v_mfma"):
+        return "mfma"
+    if op.startswith("v_"):
+        return "valu"
+    if op.startswith("s_cbranch") or op.startswith("s_branch"):
+        return "branch"
+    if op.startswith("s_waitcnt"):
+        return "wait"
+    if op.startswith("s_"):
+        return "salu"
+    if op.startswith("ds_"):
+        return "lds"
+    if op.startswith("buffer_"):
+        return "buffer"
+    return "other"
+
+
+def kernels(path):
+    """[(name, vgprs, [(label | None, mnemonic, operands)])] per function"""
+    out, cur, meta_name = [], None, None
+    vg = {}
+    with open(path) as f:
+        for line in f:
+            s = line.split(";")[0].rstrip()
+            m = re.match(r"^(\w+):\s*$", s)
+            if m and not s.startswith(".L"):
+                name, cur = m.group(1), []
+                out.append((name, cur))
+                continue
+            # metadata records list .name before .vgpr_count
+            m = re.match(r"^\s*\.name:\s*(\S+)", line)
+            if m:
+                meta_name = m.group(1)
+            m = re.match(r"^\s*\.vgpr_count:\s*(\d+)", line)
+            if m and meta_name:
+                vg[meta_name] = int(m.group(1))
+            if cur is None:
+                continue
+            if s.startswith(".Lfunc_end"):
+                cur = None
+                continue
+            m = re.match(r"^(\.LBB\w+):", s)
+            if m:
+                cur.append((m.group(1), None, None))
+                continue
+            m = re.match(r"^\s+([a-z]\w+)\s*(.*)$", s)
+            if m and not m.group(1).startswith("."):
+                cur.append((None, m.group(1), m.group(2)))
+    return [(n, vg.get(n), body) for n, body in out]
+
+
+def mfma_loops(body):
+    pos = {lab: i for i, (lab, _, _) in enumerate(body) if lab}
+    loops = []
+    for i, (lab, op, args) in enumerate(body):
+        if op and (op.startswith("s_cbranch") or op.startswith("s_branch")):
+            tgt = args.strip()
+            if tgt in pos and pos[tgt] < i:
+                seg = body[pos[tgt]:i + 1]
+                if any(o and o.startswith("v_mfma") for _, o, _ in seg):
+                    loops.append((pos[tgt], i))
+    # outermost only
+    return [l for l in loops
+            if not any(o != l and o[0] <= l[0] and l[1] <= o[1]
+                       for o in loops)]
+
+
+def mix(seg):
+    c = dict.fromkeys(COLS, 0)
+    for _, op, _ in seg:
+        if not op:
+            continue
+        c[classify(op)] += 1
+        if op.startswith(QUARTER):
+            c["quarter"] += 1
+        if "saveexec" in op:
+            c["saveexec"] += 1
+    return c
+
+
+def main():
+    path = sys.argv[1]
+    sub = sys.argv[2] if len(sys.argv) > 2 else ""
+    print("| kernel | loop | " + " | ".join(COLS) + " | VGPRs |")
+    print("|---|---|" + "---|" * (len(COLS) + 1))
+    for name, vgprs, body in kernels(path):
+        if sub not in name:
+            continue
+        for k, (a, b) in enumerate(mfma_loops(body)):
+            c = mix(body[a:b + 1])
+            print("| %s | %d | %s | %s |" % (
+                name, k, " | ".join(str(c[x]) for x in COLS), vgprs))
+
+
+if __name__ == "__main__":
+    main()

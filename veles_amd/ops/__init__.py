@@ -1267,6 +1267,14 @@ def set_halo_wgrad(on):
     _HALO_WGRAD = bool(on)
 
 
+def set_halo_wgrad_lean(on):
+    """A/B knob of the bf16 halo weight gradient's lean pixel loop (default
+    on: DMA offsets from lane invariants and carried scalars, no division
+    per step); off is the loop as it was.  Results are bit-identical."""
+    if _lib.available():
+        _lib.lib().hvk_halo_lean(int(bool(on)))
+
+
 def _halo_wgrad(x, dy, dw, dbias, N, H, W, C, OC, KH, KW, pt, pl, OH, OW,
                 groups, splits=None):
     """Stride-1 weight gradient on the halo kernel (csrc/kernels/

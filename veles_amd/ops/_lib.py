@@ -133,6 +133,7 @@ _SIGS = {
 # run (tools/gpu_bench_ab.sh) may lack; only tests and tools call them
 _OPTIONAL = {
     "hvk_hc32_handover": [I],
+    "hvk_halo_lean": [I],
     "hvk_hc_max_wgs": [I],
     # only in the -DHVK_HC_ABL build (tools/build_abl.py hc)
     "hvk_hc_stamps": [P],
