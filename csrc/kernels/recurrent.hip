@@ -1,0 +1,466 @@
+// recurrent.hip - LSTM / RNN time-step kernels on the bf16 MFMA
+// (v_mfma_f32_16x16x32_bf16, f32 accumulation; docs/OPS.md "Recurrent
+// layers"):
+//   hvk_lstm_step_fwd  acc[B][NG*H] = h_prev . Wh^T with the whole cell in the
+//                      epilogue; the pre-activations are never written;
+//   hvk_lstm_step_bwd  acc[B][H] = dG_next . Wh (from a transposed copy of
+//                      Wh) with the cell's backward in the epilogue.
+// One launch is one time step; the stream orders the steps.  No kernel waits
+// for another workgroup, nothing is atomic.
+//
+// Tile: a workgroup owns 16 hidden units x 32 batch rows and, forward, all
+// NG gates of those units (NG = 4 LSTM, gate order i f g o; NG = 1 RNN).
+// The weights are the A operand (hidden unit on the accumulator ROW), the
+// activations the B operand (batch row on the COLUMN = lane & 15): a lane
+// then holds 4 consecutive hidden units of one batch row for every gate, so
+// the cell is lane-local and every epilogue access is a 16-B / 8-B vector.
+// The weights stay [NG*H][pitch]: gate g of the tile is the row range
+// g*H + j0 ...
+// A step has few tiles and a short K, so its time is latency: the 4 waves of
+// a workgroup split K (wave w takes the 32-wide chunks w, w + 4, ...), each
+// feeding the MFMA straight from 16-B global loads held one chunk ahead, and
+// their partial sums meet in LDS, added in wave order (fixed: reruns are
+// bit-identical).  Waves 0 and 1 then run the cell for 16 batch rows each.
+#include "hvk_api.h"
+#include "hvk_common.h"
+
+using namespace hvk;
+
+namespace {
+
+constexpr int NTHR = 256;
+constexpr int NW = NTHR / WAVE;   // waves = K splits of a workgroup
+constexpr int TH = 16;            // hidden units per tile
+constexpr int BSUB = 2;           // 16-row batch sub-tiles per tile
+constexpr int TB = 16 * BSUB;     // batch rows per tile
+constexpr int BK = 32;            // K of one MFMA
+
+enum { CELL_LSTM = 0, CELL_RNN = 1 };
+
+// plain logistic function and tanh; +-inf arguments of the division give
+// exactly 0 / 1, tanhf saturates to +-1
+__device__ __forceinline__ float sigm(float x) {
+  return 1.f / (1.f + __expf(-x));
+}
+__device__ __forceinline__ float tanh_(float x) { return tanhf(x); }
+
+// The 8 bf16 [row][k .. k + 7] of a K-major operand, 0 outside rows x K.  The
+// load is unconditional (an outside fragment reads the operand's first
+// element and is replaced by 0 after): a load under a branch makes hipcc wait
+// for it where the branches join.  VEC: base and pitch on the 16-B grid and
+// K % 8 == 0, so a fragment is inside or outside as a whole.
+template <bool VEC>
+__device__ __forceinline__ bf16x8 ldfrag(const uint16_t* __restrict__ p,
+                                         long long ld, int row, int rows,
+                                         int k, int K) {
+  uint4 v;
+  if constexpr (VEC) {
+    const bool in = row < rows && k < K;
+    v = *(const uint4*)(in ? p + row * ld + k : p);
+    if (!in) v = make_uint4(0, 0, 0, 0);
+  } else {
+    uint32_t e[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool in = row < rows && k + j < K;
+      const uint16_t x = *(in ? p + row * ld + k + j : p);
+      e[j] = in ? x : 0u;
+    }
+    v = make_uint4(e[0] | e[1] << 16, e[2] | e[3] << 16, e[4] | e[5] << 16,
+                   e[6] | e[7] << 16);
+  }
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// acc[g][s] (rows: hidden units j0 .., columns: batch rows b0 + 16 s ..) =
+// sum over this wave's K chunks of W[g*H + j][k] * A[b][k]
+template <int NG, bool VEC>
+__device__ __forceinline__ void product(f32x4 (&acc)[NG][BSUB],
+                                        const uint16_t* __restrict__ W,
+                                        long long ldw, int H, int j0,
+                                        const uint16_t* __restrict__ A,
+                                        long long lda, int B, int b0, int K,
+                                        int lane, int wid) {
+  const int fr = lane & 15, fq = lane >> 4;
+  const int nkc = (K + BK - 1) / BK;
+  bf16x8 wf[NG], af[BSUB];
+  auto load = [&](int kc) {
+    const int k = kc * BK + fq * 8;   // past K in the chunk after the last
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+      wf[g] = ldfrag<VEC>(W + (long long)g * H * ldw, ldw, j0 + fr, H, k, K);
+#pragma unroll
+    for (int s = 0; s < BSUB; ++s)
+      af[s] = ldfrag<VEC>(A, lda, b0 + 16 * s + fr, B, k, K);
+  };
+  load(wid);
+  for (int kc = wid; kc < nkc; kc += NW) {
+    bf16x8 wc[NG], ac[BSUB];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) wc[g] = wf[g];
+#pragma unroll
+    for (int s = 0; s < BSUB; ++s) ac[s] = af[s];
+    load(kc + NW);
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int s = 0; s < BSUB; ++s)
+        acc[g][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wc[g], ac[s],
+                                                            acc[g][s], 0, 0, 0);
+  }
+}
+
+// The waves' partial sums through LDS; wave s < BSUB returns with the sums of
+// batch sub-tile s in out[g], added in wave order.
+template <int NG>
+__device__ __forceinline__ void reduce(const f32x4 (&acc)[NG][BSUB],
+                                       f32x4 (&out)[NG], float4* red,
+                                       int lane, int wid) {
+#pragma unroll
+  for (int g = 0; g < NG; ++g)
+#pragma unroll
+    for (int s = 0; s < BSUB; ++s) {
+      const f32x4 a = acc[g][s];
+      red[((wid * NG + g) * BSUB + s) * WAVE + lane] =
+          make_float4(a[0], a[1], a[2], a[3]);
+    }
+  __syncthreads();
+  if (wid >= BSUB) return;
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    float4 t = red[(g * BSUB + wid) * WAVE + lane];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+      const float4 u = red[((w * NG + g) * BSUB + wid) * WAVE + lane];
+      t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
+    }
+    out[g] = f32x4{t.x, t.y, t.z, t.w};
+  }
+}
+
+// 4 consecutive elements at p (nullptr: zeros); VEC: one vector access, else
+// the first n of them one by one
+template <bool VEC>
+__device__ __forceinline__ void ld4f(const float* p, int n, float* v) {
+  if constexpr (VEC) {
+    const float4 f = *(const float4*)p;
+    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = r < n ? p[r] : 0.f;
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void ld4h(const uint16_t* p, int n, float* v) {
+  if constexpr (VEC) {
+    const uint2 u = *(const uint2*)p;
+    v[0] = __uint_as_float(u.x << 16);
+    v[1] = __uint_as_float(u.x & 0xffff0000u);
+    v[2] = __uint_as_float(u.y << 16);
+    v[3] = __uint_as_float(u.y & 0xffff0000u);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = r < n ? bf2f(p[r]) : 0.f;
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void st4f(float* p, int n, const float* v) {
+  if constexpr (VEC) {
+    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (r < n) p[r] = v[r];
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void st4h(uint16_t* p, int n, const float* v) {
+  if constexpr (VEC) {
+    *(uint2*)p = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (r < n) p[r] = f2bf(v[r]);
+  }
+}
+
+struct FwdArgs {
+  const uint16_t* h_prev;   // [B][H] bf16, nullptr at step 0
+  const uint16_t* Wh;       // [NG*H][H] bf16
+  const float* xg;          // [B][NG*H] f32: x_t . Wx^T + bias
+  const float* c_prev;      // [B][H] f32, nullptr: zeros (LSTM)
+  float* c;                 // [B][H] f32 (LSTM)
+  uint16_t* h;              // [B][H] bf16
+  uint16_t* gates;          // [B][NG*H] bf16 post-activation, may be nullptr
+  long long ld_hp, ld_w, ld_xg, ld_cp, ld_c, ld_h, ld_g;
+  int B, H;
+};
+
+template <int NG, bool VEC>
+__global__ void __launch_bounds__(NTHR) step_fwd_kernel(const FwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * NG * BSUB * WAVE];
+  const int j0 = blockIdx.x * TH, b0 = blockIdx.y * TB;
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const int B = a.B, H = a.H;
+  f32x4 sum[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) sum[g] = f32x4{0, 0, 0, 0};
+  if (a.h_prev) {   // uniform over the grid
+    f32x4 acc[NG][BSUB];
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int s = 0; s < BSUB; ++s) acc[g][s] = f32x4{0, 0, 0, 0};
+    product<NG, VEC>(acc, a.Wh, a.ld_w, H, j0, a.h_prev, a.ld_hp, B, b0, H,
+                     lane, wid);
+    reduce<NG>(acc, sum, red, lane, wid);
+  }
+  if (wid >= BSUB) return;
+  const int b = b0 + 16 * wid + (lane & 15);
+  const int j = j0 + 4 * (lane >> 4);
+  if (b >= B || j >= H) return;
+  const int n = min(4, H - j);   // VEC: H % 8 == 0, so n = 4
+  float pre[NG][4];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    ld4f<VEC>(a.xg + b * a.ld_xg + (long long)g * H + j, n, pre[g]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pre[g][r] += sum[g][r];
+  }
+  float hv[4];
+  if constexpr (NG == 4) {
+    float cp[4], cv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) cp[r] = 0.f;
+    if (a.c_prev) ld4f<VEC>(a.c_prev + b * a.ld_cp + j, n, cp);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      pre[0][r] = sigm(pre[0][r]);
+      pre[1][r] = sigm(pre[1][r]);
+      pre[2][r] = tanh_(pre[2][r]);
+      pre[3][r] = sigm(pre[3][r]);
+      cv[r] = fmaf(pre[1][r], cp[r], pre[0][r] * pre[2][r]);
+      hv[r] = pre[3][r] * tanh_(cv[r]);
+    }
+    st4f<VEC>(a.c + b * a.ld_c + j, n, cv);
+    if (a.gates) {
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+        st4h<VEC>(a.gates + b * a.ld_g + (long long)g * H + j, n, pre[g]);
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) hv[r] = tanh_(pre[0][r]);
+  }
+  st4h<VEC>(a.h + b * a.ld_h + j, n, hv);
+}
+
+struct BwdArgs {
+  const uint16_t* dg_next;  // [B][NG*H] bf16: dG of step t + 1, or nullptr
+  const uint16_t* WhT;      // [H][NG*H] bf16: Wh transposed
+  const uint16_t* err;      // [B][H] bf16: error from above, or nullptr
+  const uint16_t* gates;    // LSTM: [B][4H] saved gates; RNN: h_t [B][H]
+  const float* c_prev;      // [B][H] f32, nullptr at t = 0 (LSTM)
+  const float* c;           // [B][H] f32 (LSTM)
+  const float* dc_in;       // [B][H] f32 carried dc_t, nullptr: zeros
+  float* dc_out;            // [B][H] f32 dc_{t-1} (may alias dc_in)
+  uint16_t* dg;             // [B][NG*H] bf16
+  long long ld_dgn, ld_wt, ld_e, ld_g, ld_cp, ld_c, ld_dci, ld_dco, ld_dg;
+  int B, H;
+};
+
+template <int NG, bool VEC>
+__global__ void __launch_bounds__(NTHR) step_bwd_kernel(const BwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * BSUB * WAVE];
+  const int j0 = blockIdx.x * TH, b0 = blockIdx.y * TB;
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const int B = a.B, H = a.H;
+  f32x4 sum[1] = {f32x4{0, 0, 0, 0}};
+  if (a.dg_next) {   // uniform over the grid
+    f32x4 acc[1][BSUB];
+#pragma unroll
+    for (int s = 0; s < BSUB; ++s) acc[0][s] = f32x4{0, 0, 0, 0};
+    product<1, VEC>(acc, a.WhT, a.ld_wt, H, j0, a.dg_next, a.ld_dgn, B, b0,
+                    NG * H, lane, wid);
+    reduce<1>(acc, sum, red, lane, wid);
+  }
+  if (wid >= BSUB) return;
+  const int b = b0 + 16 * wid + (lane & 15);
+  const int j = j0 + 4 * (lane >> 4);
+  if (b >= B || j >= H) return;
+  const int n = min(4, H - j);
+  float dh[4], gt[NG][4], d[NG][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) dh[r] = 0.f;
+  if (a.err) ld4h<VEC>(a.err + b * a.ld_e + j, n, dh);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) dh[r] += sum[0][r];
+#pragma unroll
+  for (int g = 0; g < NG; ++g)
+    ld4h<VEC>(a.gates + b * a.ld_g + (long long)g * H + j, n, gt[g]);
+  if constexpr (NG == 4) {
+    float cp[4], cv[4], dc[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) cp[r] = dc[r] = 0.f;
+    if (a.c_prev) ld4f<VEC>(a.c_prev + b * a.ld_cp + j, n, cp);
+    if (a.dc_in) ld4f<VEC>(a.dc_in + b * a.ld_dci + j, n, dc);
+    ld4f<VEC>(a.c + b * a.ld_c + j, n, cv);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float gi = gt[0][r], gf = gt[1][r], gg = gt[2][r], go = gt[3][r];
+      const float tc = tanh_(cv[r]);
+      const float dcr = fmaf(dh[r] * go, 1.f - tc * tc, dc[r]);
+      d[0][r] = dcr * gg * gi * (1.f - gi);
+      d[1][r] = dcr * cp[r] * gf * (1.f - gf);
+      d[2][r] = dcr * gi * (1.f - gg * gg);
+      d[3][r] = dh[r] * tc * go * (1.f - go);
+      dc[r] = dcr * gf;
+    }
+    st4f<VEC>(a.dc_out + b * a.ld_dco + j, n, dc);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      d[0][r] = dh[r] * (1.f - gt[0][r] * gt[0][r]);
+  }
+#pragma unroll
+  for (int g = 0; g < NG; ++g)
+    st4h<VEC>(a.dg + b * a.ld_dg + (long long)g * H + j, n, d[g]);
+}
+
+// y[i] = the cell's own logistic function (kind 0) / tanh (kind 1) of x[i]:
+// lets a test measure the device functions the epilogues use
+__global__ void __launch_bounds__(NTHR)
+recurrent_fn_kernel(const float* __restrict__ x, float* __restrict__ y,
+                    long long n, int kind) {
+  const long long i = (long long)blockIdx.x * NTHR + threadIdx.x;
+  if (i < n) y[i] = kind == 0 ? sigm(x[i]) : tanh_(x[i]);
+}
+
+inline bool on_grid(const void* p, long long ld) {
+  return ((uintptr_t)p & 15) == 0 && ld % 8 == 0;
+}
+
+}  // namespace
+
+// One forward time step.  cell 0 (LSTM, NG = 4, gate order i f g o):
+//   pre = xg + h_prev . Wh^T;  i, f, o = sigmoid, g = tanh;
+//   c = f c_prev + i g;  h = o tanh(c)
+// cell 1 (RNN, NG = 1): h = tanh(xg + h_prev . Wh^T); c / c_prev / gates
+// unused.  h_prev nullptr: step 0, no product.  c_prev nullptr: zeros.  gates
+// nullptr: not stored.  Every operand has its own row pitch in elements, so a
+// step of a batch-major [B][T][.] tensor is a strided view.
+HVK_API int hvk_lstm_step_fwd(int cell, int B, int H, const void* h_prev,
+                              long long ld_hp, const void* Wh, long long ld_w,
+                              const float* xg, long long ld_xg,
+                              const float* c_prev, long long ld_cp, float* c,
+                              long long ld_c, void* h, long long ld_h,
+                              void* gates, long long ld_g, hipStream_t s) {
+  const bool lstm = cell == CELL_LSTM;
+  if ((cell != CELL_LSTM && cell != CELL_RNN) || B < 1 || H < 1 || !xg ||
+      !h || (h_prev && !Wh) || (lstm && !c))
+    return -1;
+  const int ng = lstm ? 4 : 1;
+  if (ld_xg < (long long)ng * H || ld_h < H || (h_prev && ld_hp < H) ||
+      (h_prev && ld_w < H) || (lstm && ld_c < H) ||
+      (lstm && c_prev && ld_cp < H) || (lstm && gates && ld_g < 4ll * H))
+    return -1;
+  FwdArgs a;
+  a.h_prev = (const uint16_t*)h_prev;
+  a.Wh = (const uint16_t*)Wh;
+  a.xg = xg;
+  a.c_prev = lstm ? c_prev : nullptr;
+  a.c = c;
+  a.h = (uint16_t*)h;
+  a.gates = lstm ? (uint16_t*)gates : nullptr;
+  a.ld_hp = ld_hp; a.ld_w = ld_w; a.ld_xg = ld_xg; a.ld_cp = ld_cp;
+  a.ld_c = ld_c; a.ld_h = ld_h; a.ld_g = ld_g;
+  a.B = B; a.H = H;
+  const bool vec = H % 8 == 0 && on_grid(xg, ld_xg) && on_grid(h, ld_h) &&
+                   (!h_prev || (on_grid(h_prev, ld_hp) && on_grid(Wh, ld_w))) &&
+                   (!lstm || on_grid(c, ld_c)) &&
+                   (!a.c_prev || on_grid(c_prev, ld_cp)) &&
+                   (!a.gates || on_grid(gates, ld_g));
+  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
+  if (grid.y > 65535u) return -1;
+#define HVK_REC_FWD(NG, VEC) \
+  hipLaunchKernelGGL((step_fwd_kernel<NG, VEC>), grid, dim3(NTHR), 0, s, a)
+  if (lstm) {
+    if (vec) HVK_REC_FWD(4, true);
+    else HVK_REC_FWD(4, false);
+  } else {
+    if (vec) HVK_REC_FWD(1, true);
+    else HVK_REC_FWD(1, false);
+  }
+#undef HVK_REC_FWD
+  return (int)launch_status(s);
+}
+
+// One backward time step: dh = err + dg_next . Wh (either may be absent),
+// then, LSTM, from the saved gates, c_prev, c and the carried dc_in:
+//   dc = dc_in + dh o (1 - tanh(c)^2)
+//   dG = (dc g i(1-i), dc c_prev f(1-f), dc i (1-g^2), dh tanh(c) o(1-o))
+//   dc_out = dc f
+// RNN (gates = h_t): dG = dh (1 - h^2).  WhT is [H][NG*H], Wh transposed.
+HVK_API int hvk_lstm_step_bwd(int cell, int B, int H, const void* dg_next,
+                              long long ld_dgn, const void* WhT,
+                              long long ld_wt, const void* err,
+                              long long ld_e, const void* gates,
+                              long long ld_g, const float* c_prev,
+                              long long ld_cp, const float* c, long long ld_c,
+                              const float* dc_in, long long ld_dci,
+                              float* dc_out, long long ld_dco, void* dg,
+                              long long ld_dg, hipStream_t s) {
+  const bool lstm = cell == CELL_LSTM;
+  if ((cell != CELL_LSTM && cell != CELL_RNN) || B < 1 || H < 1 || !gates ||
+      !dg || (dg_next && !WhT) || (lstm && (!c || !dc_out)))
+    return -1;
+  const long long gh = (lstm ? 4ll : 1ll) * H;
+  if (ld_dg < gh || ld_g < gh || (dg_next && (ld_dgn < gh || ld_wt < gh)) ||
+      (err && ld_e < H) ||
+      (lstm && (ld_c < H || ld_dco < H || (c_prev && ld_cp < H) ||
+                (dc_in && ld_dci < H))))
+    return -1;
+  BwdArgs a;
+  a.dg_next = (const uint16_t*)dg_next;
+  a.WhT = (const uint16_t*)WhT;
+  a.err = (const uint16_t*)err;
+  a.gates = (const uint16_t*)gates;
+  a.c_prev = lstm ? c_prev : nullptr;
+  a.c = c;
+  a.dc_in = lstm ? dc_in : nullptr;
+  a.dc_out = dc_out;
+  a.dg = (uint16_t*)dg;
+  a.ld_dgn = ld_dgn; a.ld_wt = ld_wt; a.ld_e = ld_e; a.ld_g = ld_g;
+  a.ld_cp = ld_cp; a.ld_c = ld_c; a.ld_dci = ld_dci; a.ld_dco = ld_dco;
+  a.ld_dg = ld_dg;
+  a.B = B; a.H = H;
+  const bool vec = H % 8 == 0 && on_grid(dg, ld_dg) && on_grid(gates, ld_g) &&
+                   (!dg_next ||
+                    (on_grid(dg_next, ld_dgn) && on_grid(WhT, ld_wt))) &&
+                   (!err || on_grid(err, ld_e)) &&
+                   (!lstm || (on_grid(c, ld_c) && on_grid(dc_out, ld_dco))) &&
+                   (!a.c_prev || on_grid(c_prev, ld_cp)) &&
+                   (!a.dc_in || on_grid(dc_in, ld_dci));
+  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
+  if (grid.y > 65535u) return -1;
+#define HVK_REC_BWD(NG, VEC) \
+  hipLaunchKernelGGL((step_bwd_kernel<NG, VEC>), grid, dim3(NTHR), 0, s, a)
+  if (lstm) {
+    if (vec) HVK_REC_BWD(4, true);
+    else HVK_REC_BWD(4, false);
+  } else {
+    if (vec) HVK_REC_BWD(1, true);
+    else HVK_REC_BWD(1, false);
+  }
+#undef HVK_REC_BWD
+  return (int)launch_status(s);
+}
+
+HVK_API int hvk_recurrent_fn(int kind, const float* x, float* y, long long n,
+                             hipStream_t s) {
+  if (!x || !y || n < 1 || (kind != 0 && kind != 1)) return -1;
+  hipLaunchKernelGGL(recurrent_fn_kernel,
+                     dim3((unsigned)((n + NTHR - 1) / NTHR)), dim3(NTHR), 0, s,
+                     x, y, n, kind);
+  return (int)launch_status(s);
+}

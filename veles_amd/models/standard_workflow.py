@@ -50,6 +50,7 @@ from veles_amd.models.channel_splitting import (
     ChannelMerger, ChannelSplitter, GDChannelMerger, GDChannelSplitter)
 from veles_amd.models.cutter import Cutter, GDCutter
 from veles_amd.models.deconv import Deconv, GDDeconv
+from veles_amd.models.recurrent import GDLSTM, GDRNN, LSTM, RNN
 from veles_amd.models.rprop_all2all import RPropAll2All
 from veles_amd.models.standard_workflow_links import LinkBuilders
 from veles_amd.models.weights_zerofilling import GDZeroFiller, ZeroFiller
@@ -87,6 +88,8 @@ LAYER_TYPES = {
     "channel_merger": (ChannelMerger, GDChannelMerger),
     "zero_filter": (ZeroFiller, GDZeroFiller),
     "rprop_all2all": (All2All, RPropAll2All),
+    "lstm": (LSTM, GDLSTM),
+    "rnn": (RNN, GDRNN),
     "norm": (LRNormalizerForward, LRNormalizerBackward),
     "dropout": (DropoutForward, DropoutBackward),
     "activation_tanh": (act_units.ForwardTanh, act_units.BackwardTanh),

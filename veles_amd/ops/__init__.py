@@ -30,7 +30,7 @@ __all__ = ["ACT", "gemm", "linear_fwd", "conv_out_size", "conv_fwd",
            "softmax_ce", "mse", "sgd_update", "dropout", "xorshift1024star",
            "xorshift128plus", "join", "cast", "fill_minibatch",
            "mean_disp_normalize", "act_code", "kohonen_coords",
-           "kohonen_argmin", "kohonen_update"]
+           "kohonen_argmin", "kohonen_update", "lstm_fwd", "lstm_bwd"]
 
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2, torch.int32: 3,
       torch.float16: 4}
@@ -2510,3 +2510,316 @@ def kohonen_update(x, w, coords, argmin, sigma, gradient, n=None, splits=0):
     G = K[a]                                   # [n][NN]
     w += (gradient / n) * (G.t() @ xs - G.sum(0).unsqueeze(1) * w)
     return w
+
+
+# --------------------------------------------------------- recurrent layers
+# docs/OPS.md "Recurrent layers"; kernels in csrc/kernels/recurrent.hip.
+_CELLS = {"lstm": (0, 4), "rnn": (1, 1)}   # cell -> (kernel code, gates)
+
+
+def _r8(n):
+    return -(-n // 8) * 8
+
+
+def _rec_fn(name):
+    fn = getattr(_lib.lib(), name, None)
+    if fn is None:
+        raise _lib.KernelLibraryMissing(
+            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
+            (_lib.LIB_PATH, name))
+    return fn
+
+
+def _rec_buf(store, key, shape, dtype, dev, zero=False):
+    """store[key] when it fits, else a new tensor put there: a caller that
+    keeps ``store`` gets the same buffers at every call"""
+    t = store.get(key)
+    if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or \
+            t.device != dev:
+        t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype,
+                                                   device=dev)
+        store[key] = t
+    return t
+
+
+def _lstm_args(name, x, w, bias, H, cell):
+    """Shared host checks of lstm_fwd / lstm_bwd; returns (B, T, I, H, kernel
+    cell code, gates)."""
+    if cell not in _CELLS:
+        raise ValueError("%s: unknown cell %r (lstm, rnn)" % (name, cell))
+    code, ng = _CELLS[cell]
+    H = int(H)
+    if x.dim() != 3 or min(x.shape) < 1:
+        raise ValueError("%s: input must be [B][T][I], got %s" %
+                         (name, tuple(x.shape)))
+    B, T, I = x.shape
+    if H < 1 or w.dim() != 2 or tuple(w.shape) != (ng * H, I + H):
+        raise ValueError("%s: weights must be [%d][%d] (%s, I = %d, H = %d), "
+                         "got %s" % (name, ng * H, I + H, cell, I, H,
+                                     tuple(w.shape)))
+    if x.device != w.device or (bias is not None and bias.device != w.device):
+        raise ValueError("%s: operands on different devices" % name)
+    if x.stride(2) != 1 or x.stride(0) != T * x.stride(1) or w.stride(1) != 1:
+        raise ValueError("%s: input rows must be contiguous with one pitch "
+                         "over [B][T], weight rows contiguous (strides %s, "
+                         "%s)" % (name, x.stride(), w.stride()))
+    if bias is not None and (tuple(bias.shape) != (ng * H,) or
+                             not bias.is_contiguous()):
+        raise ValueError("%s: bias must be a contiguous [%d], got %s" %
+                         (name, ng * H, tuple(bias.shape)))
+    if _gpu(w):
+        if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+            raise TypeError("%s: GPU input and weights must be bfloat16, got "
+                            "%s / %s" % (name, x.dtype, w.dtype))
+        if bias is not None and bias.dtype != torch.float32:
+            raise TypeError("%s: GPU bias must be float32, got %s" %
+                            (name, bias.dtype))
+        if x.data_ptr() % 2 or w.data_ptr() % 2:
+            raise ValueError("%s: operands off the element grid" % name)
+    elif not (x.is_floating_point() and w.is_floating_point()):
+        raise TypeError("%s: floating-point operands, got %s / %s" %
+                        (name, x.dtype, w.dtype))
+    if B * T * max(_r8(ng * H), x.stride(1)) >= 1 << 31:
+        raise ValueError("%s: %d x %d x %d exceeds 2^31 elements" %
+                         (name, B, T, max(ng * H, I)))
+    return B, T, I, H, code, ng
+
+
+def _rows(x, B, T):
+    """[B][T][I] with one row pitch as a [B*T][I] view (no copy)"""
+    return x.as_strided((B * T, x.shape[2]), (x.stride(1), 1))
+
+
+def lstm_fwd(x, w, bias, H, *, cell="lstm", return_sequences=False,
+             save=None, out=None, ws=None):
+    """Forward of a recurrent layer over ``x`` [B][T][I] (batch-major).
+
+    ``w`` [NG*H][I+H] is ONE parameter: ``w[:, :I]`` is Wx, ``w[:, I:]`` is
+    Wh; NG = 4 gates in the order i, f, g, o for ``cell="lstm"``, 1 for
+    ``"rnn"``; ``bias`` [NG*H] or None.  h and c start at zero.
+
+        lstm: (i, f, o) = sigmoid, g = tanh of x_t.Wx^T + bias + h_{t-1}.Wh^T
+              c_t = f c_{t-1} + i g,  h_t = o tanh(c_t)
+        rnn:  h_t = tanh(x_t.Wx^T + bias + h_{t-1}.Wh^T)
+
+    One GEMM projects all B*T rows (float32 ``xg``), then T step launches
+    run on the current stream with no host synchronisation (capturable).
+    Returns h_T [B][H], or every h_t [B][T][H] with ``return_sequences``.
+    ``save`` (a dict) receives "h" [B][T][H], "c" [B][T][H] float32, "gates"
+    [B][T][NG*H] (post-activation; lstm only) and "xg" for lstm_bwd; with
+    ``save=None`` the gates are not written.  A kept ``save`` / ``ws`` dict
+    is reused: no allocation from the second call on."""
+    name = "lstm_fwd"
+    B, T, I, H, code, ng = _lstm_args(name, x, w, bias, H, cell)
+    dev = x.device
+    st = save if save is not None else (ws if ws is not None else {})
+    gh = ng * H
+    if out is not None and not return_sequences and (
+            tuple(out.shape) != (B, H) or out.device != dev):
+        raise ValueError("%s: out must be [%d][%d] on %s" % (name, B, H, dev))
+    if _gpu(x):
+        fn = _rec_fn("hvk_lstm_step_fwd")
+        P = _r8(gh)
+        xg_ = _rec_buf(st, "_xg", (B, T, P), torch.float32, dev)
+        h_all = _rec_buf(st, "h", (B, T, H), torch.bfloat16, dev)
+        lstm = ng == 4
+        c_all = _rec_buf(st, "c", (B, T, H), torch.float32, dev) \
+            if lstm else None
+        g_ = _rec_buf(st, "_gates", (B, T, P), torch.bfloat16, dev) \
+            if lstm and save is not None else None
+        gemm(_rows(x, B, T), w[:, :I], trans_b=True, bias=bias,
+             out=xg_.view(B * T, P)[:, :gh])
+        stream = _s(x)
+        ph, pc, pxg = h_all.data_ptr(), _p(c_all), xg_.data_ptr()
+        pg = _p(g_)
+        pw, ldw = w.data_ptr() + 2 * I, w.stride(0)
+        for t in range(T):
+            rc = fn(code, B, H,
+                    ph + 2 * (t - 1) * H if t else None, T * H, pw, ldw,
+                    pxg + 4 * t * P, T * P,
+                    pc + 4 * (t - 1) * H if lstm and t else None, T * H,
+                    pc + 4 * t * H if lstm else None, T * H,
+                    ph + 2 * t * H, T * H,
+                    pg + 2 * t * P if pg else None, T * P, stream)
+            if rc:
+                _lib.check(rc, "hvk_lstm_step_fwd")
+        if save is not None:
+            save["xg"] = xg_[:, :, :gh]
+            if lstm:
+                save["gates"] = g_[:, :, :gh]
+    else:
+        xf, wf = x.float(), w.float()
+        xg = xf.reshape(B * T, I) @ wf[:, :I].t()
+        if bias is not None:
+            xg = xg + bias.float().view(1, -1)
+        xg = xg.view(B, T, gh)
+        wh = wf[:, I:]
+        h_all = _rec_buf(st, "h", (B, T, H), torch.float32, dev)
+        h = torch.zeros(B, H)
+        if ng == 4:
+            c_all = _rec_buf(st, "c", (B, T, H), torch.float32, dev)
+            gates = _rec_buf(st, "gates", (B, T, gh), torch.float32, dev)
+            c = torch.zeros(B, H)
+        for t in range(T):
+            pre = xg[:, t] + h @ wh.t() if t else xg[:, t]
+            if ng == 4:
+                gi = torch.sigmoid(pre[:, :H])
+                gf = torch.sigmoid(pre[:, H:2 * H])
+                gg = torch.tanh(pre[:, 2 * H:3 * H])
+                go = torch.sigmoid(pre[:, 3 * H:])
+                c = gf * c + gi * gg
+                h = go * torch.tanh(c)
+                c_all[:, t] = c
+                gates[:, t] = torch.cat((gi, gf, gg, go), 1)
+            else:
+                h = torch.tanh(pre)
+            h_all[:, t] = h
+        if save is not None:
+            save["xg"] = xg
+    if return_sequences:
+        return h_all
+    last = h_all[:, T - 1]
+    if out is None:
+        return last.contiguous()
+    out.copy_(last)
+    return out
+
+
+def lstm_bwd(err, x, w, save, dw, dbias, *, cell="lstm", accumulate="overwrite",
+             need_err_input=True, err_input=None):
+    """Backward of lstm_fwd from its ``save`` dict.
+
+    ``err`` is dL/dh_T [B][H], or dL/dh_t for every step [B][T][H] (the
+    layer ran with ``return_sequences``).  T step launches (t = T-1 .. 0)
+    fill save["dg"] = dL/d(pre-activations) [B][T][NG*H]; then
+    ``dw[:, :I]`` (+)= dG^T.X with ``dbias`` (+)= its column sums,
+    ``dw[:, I:]`` (+)= dG^T.H_prev over all B*T rows (``accumulate``: True
+    adds, "overwrite" writes, as in ``gemm``), and, with ``need_err_input``,
+    err_input [B][T][I] = dG.Wx is returned.  ``dw`` is float32 [NG*H][I+H], ``dbias`` float32 [NG*H] or
+    None.  Bit-reproducible under ``set_deterministic(True)``."""
+    name = "lstm_bwd"
+    if cell not in _CELLS:
+        raise ValueError("%s: unknown cell %r (lstm, rnn)" % (name, cell))
+    ng = _CELLS[cell][1]
+    if w.dim() != 2 or w.shape[0] % ng:
+        raise ValueError("%s: weights %s" % (name, tuple(w.shape)))
+    B, T, I, H, code, ng = _lstm_args(name, x, w, None, w.shape[0] // ng,
+                                      cell)
+    dev = x.device
+    gh = ng * H
+    lstm = ng == 4
+    if accumulate not in (True, "overwrite"):
+        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
+                         name)
+    seq = err.dim() == 3
+    if tuple(err.shape) != ((B, T, H) if seq else (B, H)) or \
+            err.stride(-1) != 1 or err.device != dev:
+        raise ValueError("%s: err must be [%d][%d] or [%d][%d][%d] with "
+                         "contiguous rows on %s, got %s" %
+                         (name, B, H, B, T, H, dev, tuple(err.shape)))
+    if dw.dtype != torch.float32 or tuple(dw.shape) != (gh, I + H) or \
+            dw.stride(1) != 1 or dw.device != dev:
+        raise ValueError("%s: dw must be float32 [%d][%d] on %s" %
+                         (name, gh, I + H, dev))
+    if dbias is not None and (dbias.dtype != torch.float32 or
+                              tuple(dbias.shape) != (gh,) or
+                              not dbias.is_contiguous() or
+                              dbias.device != dev):
+        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
+                         % (name, gh, dev))
+    hdt = torch.bfloat16 if _gpu(x) else torch.float32
+    need = [("h", (B, T, H), hdt)]
+    if lstm:
+        need += [("c", (B, T, H), torch.float32), ("gates", (B, T, gh), hdt)]
+    for k, shape, dt in need:
+        t = None if save is None else save.get(k)
+        if t is None or tuple(t.shape) != shape or t.dtype != dt or \
+                t.device != dev:
+            raise ValueError("%s: save[%r] must be %s %s from lstm_fwd" %
+                             (name, k, dt, shape))
+    if need_err_input and err_input is not None and (
+            tuple(err_input.shape) != (B, T, I) or
+            not err_input.is_contiguous() or err_input.device != dev or
+            err_input.dtype != hdt):
+        raise ValueError("%s: err_input must be a contiguous %s [%d][%d][%d]"
+                         % (name, hdt, B, T, I))
+    h_all = save["h"]
+    if _gpu(x):
+        if err.dtype != torch.bfloat16:
+            raise TypeError("%s: GPU err must be bfloat16, got %s" %
+                            (name, err.dtype))
+        fn = _rec_fn("hvk_lstm_step_bwd")
+        P = _r8(gh)
+        g_ = save.get("_gates")
+        if lstm and (g_ is None or tuple(g_.shape) != (B, T, P) or
+                     g_.data_ptr() != save["gates"].data_ptr()):
+            raise ValueError("%s: save[\"gates\"] is not lstm_fwd's" % name)
+        # Wh^T, one copy per call: the product of a step sums over Wh's rows
+        wt = _rec_buf(save, "_wht", (H, P), torch.bfloat16, dev)
+        wt[:, :gh].copy_(w[:, I:].t())
+        dg_ = _rec_buf(save, "_dg", (B, T, P), torch.bfloat16, dev, zero=True)
+        # dc[t] = dL/dc_{t-1} as step t leaves it (read by step t - 1)
+        dc = _rec_buf(save, "dc", (T, B, H), torch.float32, dev) \
+            if lstm else None
+        stream = _s(x)
+        pdg, pwt, pdc = dg_.data_ptr(), wt.data_ptr(), _p(dc)
+        pgt = g_.data_ptr() if lstm else h_all.data_ptr()
+        ldgt = T * P if lstm else T * H
+        pc = save["c"].data_ptr() if lstm else None
+        pe = err.data_ptr()
+        lde = err.stride(0)
+        for t in range(T - 1, -1, -1):
+            last = t == T - 1
+            rc = fn(code, B, H,
+                    None if last else pdg + 2 * (t + 1) * P, T * P, pwt, P,
+                    pe + 2 * t * err.stride(1) if seq else
+                    (pe if last else None), lde,
+                    pgt + 2 * t * (P if lstm else H), ldgt,
+                    pc + 4 * (t - 1) * H if lstm and t else None, T * H,
+                    pc + 4 * t * H if lstm else None, T * H,
+                    None if last or not lstm else pdc + 4 * (t + 1) * B * H,
+                    H, pdc + 4 * t * B * H if lstm else None, H,
+                    pdg + 2 * t * P, T * P, stream)
+            if rc:
+                _lib.check(rc, "hvk_lstm_step_bwd")
+        dg = dg_[:, :, :gh]
+        dg2 = dg_.view(B * T, P)[:, :gh]
+    else:
+        wh = w.float()[:, I:]
+        dg = _rec_buf(save, "dg", (B, T, gh), torch.float32, dev)
+        dc = torch.zeros(B, H)
+        ef = err.float()
+        for t in range(T - 1, -1, -1):
+            dh = ef[:, t] if seq else (ef if t == T - 1 else
+                                       torch.zeros(B, H))
+            if t < T - 1:
+                dh = dh + dg[:, t + 1] @ wh
+            if lstm:
+                gi, gf, gg, go = save["gates"][:, t].float().split(H, 1)
+                tc = torch.tanh(save["c"][:, t])
+                cp = save["c"][:, t - 1] if t else torch.zeros(B, H)
+                dc = dc + dh * go * (1.0 - tc * tc)
+                dg[:, t] = torch.cat((dc * gg * gi * (1.0 - gi),
+                                      dc * cp * gf * (1.0 - gf),
+                                      dc * gi * (1.0 - gg * gg),
+                                      dh * tc * go * (1.0 - go)), 1)
+                dc = dc * gf
+            else:
+                ht = h_all[:, t].float()
+                dg[:, t] = dh * (1.0 - ht * ht)
+        dg2 = dg.view(B * T, gh)
+    save["dg"] = dg
+    # h_{t-1} of every row: h shifted by one step, zeros at t = 0
+    hp = _rec_buf(save, "_hprev", (B, T, H), hdt, dev, zero=True)
+    if T > 1:
+        hp[:, 1:].copy_(h_all[:, :T - 1])
+    gemm(dg2, _rows(x, B, T), trans_a=True, out=dw[:, :I],
+         accumulate=accumulate, bias_grad=dbias)
+    gemm(dg2, hp.view(B * T, H), trans_a=True, out=dw[:, I:],
+         accumulate=accumulate)
+    if not need_err_input:
+        return None
+    if err_input is None:
+        err_input = torch.empty(B, T, I, dtype=hdt, device=dev)
+    gemm(dg2, w[:, :I], out=err_input.view(B * T, I))
+    return err_input

@@ -142,6 +142,13 @@ _OPTIONAL = {
     # B, NN, D, ldx, inv2sigma2, gmult, ws, splits, s)
     "hvk_kohonen_argmin": [P, I, P, I, I, I, I, P, P, P, P, I, P],
     "hvk_kohonen_update": [P, I, P, P, P, I, I, I, I, F, F, P, I, P],
+    # recurrent layers (csrc/kernels/recurrent.hip), every operand followed
+    # by its row pitch: (cell, B, H, h_prev, Wh, xg, c_prev, c, h, gates, s)
+    # and (cell, B, H, dg_next, WhT, err, gates, c_prev, c, dc_in, dc_out,
+    # dg, s); (kind, x, y, n, s)
+    "hvk_lstm_step_fwd": [I, I, I] + [P, L] * 7 + [P],
+    "hvk_lstm_step_bwd": [I, I, I] + [P, L] * 9 + [P],
+    "hvk_recurrent_fn": [I, P, P, L, P],
 }
 # functions returning a pointer / a 64-bit int (every other one returns int)
 _PTR_RET = {"hvk_stream_create"}
