@@ -487,7 +487,10 @@ def _gemm_fx(a, b, ta, tb, out, M, N, K, alpha, beta, accumulate, level,
         raise TypeError("gemm: mixed %s / %s / %s operands" %
                         (a.dtype, b.dtype, out.dtype))
     for t in (a, b, out):
-        if t.stride(-1) != 1:
+        # a single column has no inner stride to speak of: torch keeps
+        # whatever the tensor it was viewed from had ([1][K].t() is [K][1]
+        # with strides (1, K)); its row pitch stride(0) is still right
+        if t.stride(-1) != 1 and t.shape[-1] != 1:
             raise ValueError("gemm operands must be row-major")
     name = "hvk_gemm_f32" if a.dtype == torch.float32 else "hvk_gemm_f64"
     _lib_call(name, int(ta), int(tb), M, N, K, _p(a), a.stride(0), _p(b),
