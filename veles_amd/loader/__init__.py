@@ -8,6 +8,7 @@ from veles_amd.loader.fullbatch import (  # noqa: F401
 from veles_amd.loader.synthetic import (  # noqa: F401
     SyntheticImageLoader, SyntheticMSELoader)
 from veles_amd.loader.seq_recall import SeqRecallLoader  # noqa: F401
+from veles_amd.loader.bars_stripes import BarsStripesLoader  # noqa: F401
 from veles_amd.loader.image import (  # noqa: F401
     ImageLoader, FileImageLoader, AutoLabelFileImageLoader,
     FileListImageLoader, FullBatchFileImageLoader,

@@ -30,7 +30,8 @@ __all__ = ["ACT", "gemm", "linear_fwd", "conv_out_size", "conv_fwd",
            "softmax_ce", "mse", "sgd_update", "dropout", "xorshift1024star",
            "xorshift128plus", "join", "cast", "fill_minibatch",
            "mean_disp_normalize", "act_code", "kohonen_coords",
-           "kohonen_argmin", "kohonen_update", "lstm_fwd", "lstm_bwd"]
+           "kohonen_argmin", "kohonen_update", "lstm_fwd", "lstm_bwd",
+           "rbm_layout", "rbm_uniforms", "rbm_sample", "rbm_grad"]
 
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2, torch.int32: 3,
       torch.float16: 4}
@@ -2826,3 +2827,201 @@ def lstm_bwd(err, x, w, save, dw, dbias, *, cell="lstm", accumulate="overwrite",
         err_input = torch.empty(B, T, I, dtype=hdt, device=dev)
     gemm(dg2, w[:, :I], out=err_input.view(B * T, I))
     return err_input
+
+
+# ------------------------------------------- restricted Boltzmann machines
+# docs/OPS.md "Restricted Boltzmann machines"; kernels in csrc/kernels/rbm.hip.
+def _rbm_fn(name):
+    fn = getattr(_lib.lib(), name, None)
+    if fn is None:
+        raise _lib.KernelLibraryMissing(
+            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
+            (_lib.LIB_PATH, name))
+    return fn
+
+
+def rbm_layout(V, H):
+    """(offset of hbias, offset of vbias, length) of the flat float32 buffer
+    [W [H][V] | hbias [H] | vbias [V]]: every segment starts on a 16-element
+    boundary."""
+    V, H = int(V), int(H)
+    hb = -(-(H * V) // 16) * 16
+    vb = hb + -(-H // 16) * 16
+    return hb, vb, vb + -(-V // 16) * 16
+
+
+def rbm_uniforms(rows, N, seed, base=0, device="cpu"):
+    """The float32 uniforms [rows][N] of one sampling call: element (b, j) is
+    (hash32(base + b N + j, seed) >> 8) 2^-24, indices modulo 2^32."""
+    i = (torch.arange(rows * N, dtype=torch.int64, device=device) +
+         (int(base) & 0xFFFFFFFF)) & 0xFFFFFFFF
+    u = (_hash32(i, int(seed) & 0xFFFFFFFF) >> 8).float() / 16777216.0
+    return u.view(rows, N)
+
+
+def _rbm_mat(name, what, t, rows, cols, dev, gpu):
+    """A [rows][cols] operand with contiguous rows and one row pitch."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError("%s: %s must be a 2-D tensor" % (name, what))
+    if (rows is not None and t.shape[0] != rows) or t.shape[1] != cols:
+        raise ValueError("%s: %s must be [%s][%d], got %s" % (
+            name, what, "rows" if rows is None else rows, cols,
+            tuple(t.shape)))
+    if t.device != dev:
+        raise ValueError("%s: %s on %s, weights on %s" % (name, what,
+                                                         t.device, dev))
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < cols):
+        raise ValueError("%s: %s rows must be contiguous (strides %s)" %
+                         (name, what, t.stride()))
+    if gpu:
+        if t.dtype != torch.bfloat16:
+            raise TypeError("%s: GPU %s must be bfloat16, got %s" %
+                            (name, what, t.dtype))
+    elif not t.is_floating_point():
+        raise TypeError("%s: %s must be floating-point, got %s" %
+                        (name, what, t.dtype))
+    ld = t.stride(0) if t.shape[0] > 1 else max(cols, t.stride(0))
+    if t.shape[0] * ld >= 1 << 31:
+        raise ValueError("%s: %s %d x %d exceeds 2^31 elements" %
+                         (name, what, t.shape[0], ld))
+    return ld
+
+
+def rbm_sample(x, w, bias, *, transposed=False, n=None, probs=None,
+               sample=None, seed=0, seed_dev=None, base=0):
+    """One half of a Gibbs step from the weights ``w`` [H][V]:
+
+        transposed=False: x [rows][V] -> p = sigmoid(x . w^T + bias) [rows][H]
+        transposed=True:  x [rows][H] -> p = sigmoid(x . w   + bias) [rows][V]
+
+    (the same ``w``: no transposed copy exists), ``probs`` = p and ``sample``
+    = 1 where u < p else 0, with the uniform of element (b, j) of the
+    [rows][N] output u = (hash32(base + b N + j, seed) >> 8) 2^-24
+    (:func:`rbm_uniforms`) compared in float32 before any bfloat16 rounding.
+    Only the first ``n`` rows are read and written.  Either output may be
+    None, not both.  ``seed_dev`` (int32 [1] on the device) replaces
+    ``seed``.  GPU: x, w, probs, sample bfloat16, bias float32; one launch,
+    no synchronisation.  Returns (probs, sample)."""
+    name = "rbm_sample"
+    if not isinstance(w, torch.Tensor) or w.dim() != 2 or min(w.shape) < 1:
+        raise ValueError("%s: weights must be [H][V]" % name)
+    gpu = _gpu(w)
+    dev = w.device
+    H, V = w.shape
+    K, U = (H, V) if transposed else (V, H)
+    ldw = _rbm_mat(name, "weights", w, H, V, dev, gpu)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError("%s: input must be [rows][%d]" % (name, K))
+    rows = x.shape[0]
+    ldx = _rbm_mat(name, "input", x, rows, K, dev, gpu)
+    if probs is None and sample is None:
+        raise ValueError("%s: neither probs nor sample is wanted" % name)
+    ldp = lds = 0
+    if probs is not None:
+        ldp = _rbm_mat(name, "probs", probs, rows, U, dev, gpu)
+    if sample is not None:
+        lds = _rbm_mat(name, "sample", sample, rows, U, dev, gpu)
+    if not isinstance(bias, torch.Tensor) or tuple(bias.shape) != (U,) or \
+            not bias.is_contiguous() or bias.device != dev:
+        raise ValueError("%s: bias must be a contiguous [%d] on %s" %
+                         (name, U, dev))
+    if gpu and bias.dtype != torch.float32:
+        raise TypeError("%s: GPU bias must be float32, got %s" %
+                        (name, bias.dtype))
+    if not bias.is_floating_point():
+        raise TypeError("%s: bias must be floating-point" % name)
+    n = rows if n is None else int(n)
+    if n < 1 or n > rows:
+        raise ValueError("%s: %d valid rows of %d" % (name, n, rows))
+    base = int(base)
+    if base < 0:
+        raise ValueError("%s: base %d" % (name, base))
+    if seed_dev is not None and (
+            not isinstance(seed_dev, torch.Tensor) or
+            seed_dev.dtype != torch.int32 or seed_dev.numel() != 1 or
+            seed_dev.device != dev):
+        raise ValueError("%s: seed_dev must be an int32 [1] on %s" %
+                         (name, dev))
+    if gpu:
+        _lib.check(_rbm_fn("hvk_rbm_sample")(
+            1 if transposed else 0, n, V, H, _p(x), ldx, _p(w), ldw,
+            _p(bias), _p(probs), ldp, _p(sample), lds,
+            int(seed) & 0xFFFFFFFF, _p(seed_dev), base & 0xFFFFFFFF, _s(w)),
+            "hvk_rbm_sample")
+        return probs, sample
+    if seed_dev is not None:
+        seed = int(seed_dev.reshape(-1)[0]) & 0xFFFFFFFF
+    xf, wf = x[:n].float(), w.float()
+    pre = (xf @ wf if transposed else xf @ wf.t()) + bias.float().view(1, -1)
+    p = 1.0 / (1.0 + torch.exp(-pre))
+    if probs is not None:
+        probs[:n] = p.to(probs.dtype)
+    if sample is not None:
+        u = rbm_uniforms(n, U, seed, base)
+        sample[:n] = (u < p).to(sample.dtype)
+    return probs, sample
+
+
+def rbm_grad(v0, h0, vk, hk, grad, *, n=None, scale=None, splits=0):
+    """The contrastive-divergence statistic over the first ``n`` rows,
+    OVERWRITING the flat float32 buffer ``grad`` (:func:`rbm_layout`):
+
+        W     = scale (h0^T . v0 - hk^T . vk)          [H][V]
+        hbias = scale sum_b (h0 - hk),  vbias = scale sum_b (v0 - vk)
+
+    ``scale`` defaults to -1/n (the gradient a descent step subtracts); the
+    padding between the segments is set to 0.  v0 / vk are [rows][V], h0 / hk
+    [rows][H] (bfloat16 on the GPU).  ``splits`` forces the number of batch
+    slices on the GPU (0: chosen); the slices are added in order, so the
+    result does not depend on scheduling."""
+    name = "rbm_grad"
+    for what, t in (("v0", v0), ("h0", h0), ("vk", vk), ("hk", hk),
+                    ("grad", grad)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a tensor" % (name, what))
+    if v0.dim() != 2 or h0.dim() != 2 or min(v0.shape) < 1 or \
+            min(h0.shape) < 1:
+        raise ValueError("%s: v0 must be [rows][V], h0 [rows][H]" % name)
+    rows, V = v0.shape
+    H = h0.shape[1]
+    gpu = _gpu(grad)
+    dev = grad.device
+    ld_v0 = _rbm_mat(name, "v0", v0, rows, V, dev, gpu)
+    ld_h0 = _rbm_mat(name, "h0", h0, rows, H, dev, gpu)
+    ld_vk = _rbm_mat(name, "vk", vk, rows, V, dev, gpu)
+    ld_hk = _rbm_mat(name, "hk", hk, rows, H, dev, gpu)
+    off_hb, off_vb, total = rbm_layout(V, H)
+    if grad.dtype != torch.float32:
+        raise TypeError("%s: grad must be float32, got %s" %
+                        (name, grad.dtype))
+    if grad.dim() != 1 or grad.numel() != total or not grad.is_contiguous():
+        raise ValueError("%s: grad must be a contiguous flat [%d] (V %d, H "
+                         "%d), got %s" % (name, total, V, H,
+                                          tuple(grad.shape)))
+    if H * V >= 1 << 31:
+        raise ValueError("%s: %d x %d weights exceed 2^31 elements" %
+                         (name, H, V))
+    n = rows if n is None else int(n)
+    if n < 1 or n > rows:
+        raise ValueError("%s: %d valid rows of %d" % (name, n, rows))
+    splits = int(splits)
+    if splits < 0:
+        raise ValueError("%s: splits %d" % (name, splits))
+    scale = -1.0 / n if scale is None else float(scale)
+    if gpu:
+        sp = _rbm_fn("hvk_rbm_grad_splits")(n, V, H, splits)
+        if sp < 1 or sp > 65535:
+            raise ValueError("%s: %d splits for %d rows" % (name, splits, n))
+        ws = None if sp == 1 else _grow_ws("rbm_grad", sp * total,
+                                           torch.float32, dev)
+        _lib.check(_rbm_fn("hvk_rbm_grad")(
+            n, V, H, _p(v0), ld_v0, _p(h0), ld_h0, _p(vk), ld_vk, _p(hk),
+            ld_hk, _p(grad), scale, _p(ws), sp, _s(grad)), "hvk_rbm_grad")
+        return grad
+    a0, b0 = h0[:n].float(), v0[:n].float()
+    ak, bk = hk[:n].float(), vk[:n].float()
+    grad.zero_()
+    grad[:H * V] = (scale * (a0.t() @ b0 - ak.t() @ bk)).reshape(-1)
+    grad[off_hb:off_hb + H] = scale * (a0 - ak).sum(0)
+    grad[off_vb:off_vb + V] = scale * (b0 - bk).sum(0)
+    return grad

@@ -149,6 +149,13 @@ _OPTIONAL = {
     "hvk_lstm_step_fwd": [I, I, I] + [P, L] * 7 + [P],
     "hvk_lstm_step_bwd": [I, I, I] + [P, L] * 9 + [P],
     "hvk_recurrent_fn": [I, P, P, L, P],
+    # restricted Boltzmann machines (csrc/kernels/rbm.hip): (transposed, n,
+    # V, H, x, ldx, w, ldw, bias, probs, ldp, sample, lds, seed, seed_dev,
+    # base, s); (n, V, H, splits); (n, V, H, v0, h0, vk, hk each with its
+    # pitch, grad, scale, ws, splits, s)
+    "hvk_rbm_sample": [I, I, I, I, P, L, P, L, P, P, L, P, L, U, P, L, P],
+    "hvk_rbm_grad_splits": [I, I, I, I],
+    "hvk_rbm_grad": [I, I, I] + [P, L] * 4 + [P, F, P, I, P],
 }
 # functions returning a pointer / a 64-bit int (every other one returns int)
 _PTR_RET = {"hvk_stream_create"}
