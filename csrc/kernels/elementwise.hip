@@ -313,6 +313,21 @@ struct SgdSeg {
   long long begin, end;
   float lr, decay, l1, moment;
 };
+// The table is sorted and disjoint; an element outside every segment (before
+// the first begin, in a gap, past the last end) is left untouched, but its
+// w_lp is still written and its gradient still cleared from zero_from on.
+__device__ __forceinline__ float sgd_step(float wi, float graw, float mq,
+                                          const SgdSeg& sg, float gscale) {
+  // the fmas spelled out, so the whole-float4 and the element-by-element
+  // path of sgd4_kernel round alike wherever the compiler would contract
+  float g = graw * gscale;
+  if (sg.decay != 0.f) {
+    const float sgn = wi > 0.f ? 1.f : (wi < 0.f ? -1.f : 0.f);
+    g = __builtin_fmaf(sg.decay,
+                       __builtin_fmaf(1.f - sg.l1, wi, sg.l1 * sgn), g);
+  }
+  return __builtin_fmaf(sg.moment, mq, -(sg.lr * g));
+}
 __global__ void sgd4_kernel(float4* w, float4* grad, float4* mom,
                             uint2* w_lp, const SgdSeg* segs, int nseg,
                             long long total4, float gscale,
@@ -331,24 +346,41 @@ __global__ void sgd4_kernel(float4* w, float4* grad, float4* mom,
     float* wp = (float*)&wv;
     float* gp = (float*)&gv;
     float* mp = (float*)&mv;
-    bool in = e >= sg.begin && e < sg.end;
+    if (e >= sg.begin && e + 4 <= sg.end &&
+        (zero_from <= e || zero_from >= e + 4)) {
+      // the whole float4 in one segment and on one side of zero_from
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float wi = wp[q];
-      float g = gp[q] * gscale;
-      if (sg.decay != 0.f)
-        g += sg.decay * ((1.f - sg.l1) * wi +
-                         sg.l1 * (wi > 0.f ? 1.f : (wi < 0.f ? -1.f : 0.f)));
-      float v = -sg.lr * g + sg.moment * mp[q];
-      if (!in) v = 0.f;
-      mp[q] = in ? v : mp[q];
-      wp[q] = wi + v;
+      for (int q = 0; q < 4; ++q) {
+        float v = sgd_step(wp[q], gp[q], mp[q], sg, gscale);
+        mp[q] = v;
+        wp[q] += v;
+      }
+      w[i] = wv;
+      if (mom) mom[i] = mv;
+      // gradients at and past zero_from (a parameter offset) are cleared
+      // for the next step's split-K atomics
+      if (e >= zero_from) grad[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      // a segment end, a gap or zero_from inside the float4 (parameters end
+      // at offset + size, seldom on the 4-grid): element by element, each
+      // with its own segment
+      int k = lo;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const long long eq = e + q;
+        while (k + 1 < nseg && segs[k + 1].begin <= eq) ++k;
+        const SgdSeg sq = segs[k];
+        if (eq >= sq.begin && eq < sq.end) {
+          float v = sgd_step(wp[q], gp[q], mp[q], sq, gscale);
+          mp[q] = v;
+          wp[q] += v;
+        }
+        if (eq >= zero_from) gp[q] = 0.f;
+      }
+      w[i] = wv;
+      if (mom) mom[i] = mv;
+      if (e + 3 >= zero_from) grad[i] = gv;
     }
-    w[i] = wv;
-    if (mom) mom[i] = mv;
-    // gradients at and past zero_from (a 64-aligned parameter offset) are
-    // cleared for the next step's split-K atomics
-    if (e >= zero_from) grad[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (w_lp) {
       uint2 o;
       o.x = f2bf(wp[0]) | ((uint32_t)f2bf(wp[1]) << 16);
@@ -371,16 +403,18 @@ __global__ void sgd_kernel(float* w, const float* grad, float* mom,
     }
     const SgdSeg sg = segs[lo];
     float wi = w[i];
-    float g = grad[i] * gscale;
-    if (sg.decay != 0.f)
-      g += sg.decay * ((1.f - sg.l1) * wi + sg.l1 * (wi > 0.f ? 1.f : (wi < 0.f ? -1.f : 0.f)));
-    float v = -sg.lr * g;
-    if (mom) {
-      v += sg.moment * mom[i];
-      mom[i] = v;
+    if (i >= sg.begin && i < sg.end) {
+      float g = grad[i] * gscale;
+      if (sg.decay != 0.f)
+        g += sg.decay * ((1.f - sg.l1) * wi + sg.l1 * (wi > 0.f ? 1.f : (wi < 0.f ? -1.f : 0.f)));
+      float v = -sg.lr * g;
+      if (mom) {
+        v += sg.moment * mom[i];
+        mom[i] = v;
+      }
+      wi += v;
+      w[i] = wi;
     }
-    wi += v;
-    w[i] = wi;
     if (w_lp) w_lp[i] = f2bf(wi);
   }
 }
@@ -777,6 +811,7 @@ __global__ void space_to_depth_kernel(const uint16_t* __restrict__ x,
 //   3 rprop     (iRprop-) s1 = step, s2 = previous gradient:
 //               same sign -> step*1.2 (<= 50), flip -> step*0.5 (>= 1e-6),
 //               g = 0 ; w -= sign(g)*step ; s2 = g
+// An element outside every segment keeps w, s1 and s2 (see SgdSeg).
 struct SolverSeg {
   long long begin, end;
   float lr, decay, l1, moment;
@@ -796,7 +831,7 @@ __global__ void solver_kernel(float* w, float* grad, float* s1, float* s2,
     }
     const SolverSeg sg = segs[lo];
     float wi = w[i];
-    if (i < sg.end) {
+    if (i >= sg.begin && i < sg.end) {
       float g = grad[i] * gscale;
       if (sg.decay != 0.f)
         g += sg.decay * ((1.f - sg.l1) * wi +
@@ -819,8 +854,11 @@ __global__ void solver_kernel(float* w, float* grad, float* s1, float* s2,
         case 3: {
           float step = s1[i] > 0.f ? s1[i] : sg.lr;
           float pg = s2[i];
-          if (pg * g > 0.f) step = fminf(step * 1.2f, 50.f);
-          else if (pg * g < 0.f) { step = fmaxf(step * 0.5f, 1e-6f); g = 0.f; }
+          // by the signs: the product of two tiny gradients underflows
+          const bool up = (pg > 0.f && g > 0.f) || (pg < 0.f && g < 0.f);
+          const bool down = (pg > 0.f && g < 0.f) || (pg < 0.f && g > 0.f);
+          if (up) step = fminf(step * 1.2f, 50.f);
+          else if (down) { step = fmaxf(step * 0.5f, 1e-6f); g = 0.f; }
           wi -= (g > 0.f ? step : (g < 0.f ? -step : 0.f));
           s1[i] = step;
           s2[i] = g;
@@ -1659,6 +1697,14 @@ HVK_API int hvk_act_bwd(const void* dy, int dydt, const void* y, int ydt,
   return (int)launch_status(s);
 }
 
+// keep(i) = hash >= thresh, thresh = floor(p * 2^32) from the float32 p (the
+// product is exact in double), at most 2^32 - 1
+static uint32_t dropout_thresh(float p) {
+  const double t = (double)p * 4294967296.0;
+  if (!(t >= 1.0)) return 0u;
+  return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+}
+
 static void launch_dropout(const void* x, int xdt, void* y, int ydt,
                            long long n, uint32_t seed, uint32_t thresh,
                            float scale, void* mask_out, const void* seed_dev,
@@ -1678,7 +1724,7 @@ static void launch_dropout(const void* x, int xdt, void* y, int ydt,
 
 HVK_API int hvk_dropout(const void* x, int xdt, void* y, int ydt, long long n,
                         unsigned seed, float p, void* mask_out, hipStream_t s) {
-  uint32_t thresh = (uint32_t)fminf(4294967295.f, p * 4294967296.f);
+  uint32_t thresh = dropout_thresh(p);
   float scale = p < 1.f ? 1.f / (1.f - p) : 0.f;
   launch_dropout(x, xdt, y, ydt, n, seed, thresh, scale, mask_out, nullptr,
                  0ll, s);
@@ -1690,7 +1736,7 @@ HVK_API int hvk_dropout(const void* x, int xdt, void* y, int ydt, long long n,
 HVK_API int hvk_dropout_dev(const void* x, int xdt, void* y, int ydt,
                             long long n, const void* seed_dev, float p,
                             void* mask_out, hipStream_t s) {
-  uint32_t thresh = (uint32_t)fminf(4294967295.f, p * 4294967296.f);
+  uint32_t thresh = dropout_thresh(p);
   float scale = p < 1.f ? 1.f / (1.f - p) : 0.f;
   launch_dropout(x, xdt, y, ydt, n, 0u, thresh, scale, mask_out, seed_dev,
                  0ll, s);
@@ -1701,7 +1747,7 @@ HVK_API int hvk_dropout_dev(const void* x, int xdt, void* y, int ydt,
 HVK_API int hvk_dropout_dev_at(const void* x, int xdt, void* y, int ydt,
                                long long n, const void* seed_dev, float p,
                                long long base, hipStream_t s) {
-  uint32_t thresh = (uint32_t)fminf(4294967295.f, p * 4294967296.f);
+  uint32_t thresh = dropout_thresh(p);
   float scale = p < 1.f ? 1.f / (1.f - p) : 0.f;
   launch_dropout(x, xdt, y, ydt, n, 0u, thresh, scale, nullptr, seed_dev,
                  base, s);

@@ -570,6 +570,7 @@ def test_solver_kernel(mode):
         assert float(gg.abs().max()) == 0.0
     close(wg, wc, 1e-5)
     close(s1g, s1c, 1e-5)
+    close(s2g, s2c, 1e-5)
     close(lp.float(), wc, 1e-2)
 
 

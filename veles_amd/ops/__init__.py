@@ -2074,8 +2074,9 @@ def solver_update(w, grad, s1, s2, segs, w_lp=None, gscale=1.0,
         elif mode == 3:
             prev = s2[b:e]
             step = torch.where(a > 0, a, torch.full_like(a, lr))
-            same = prev * g > 0
-            flip = prev * g < 0
+            # by the signs, not the product: tiny gradients underflow it
+            same = torch.sign(prev) * torch.sign(g) > 0
+            flip = torch.sign(prev) * torch.sign(g) < 0
             step = torch.where(same, (step * 1.2).clamp(max=50.0), step)
             step = torch.where(flip, (step * 0.5).clamp(min=1e-6), step)
             g = torch.where(flip, torch.zeros_like(g), g)
@@ -2104,11 +2105,21 @@ def _hash32(i, seed):
     return x
 
 
+def _f32(x):
+    """x rounded to float32, as the kernel library receives it."""
+    return struct.unpack("<f", struct.pack("<f", float(x)))[0]
+
+
+def dropout_thresh(p):
+    """Elements whose hash is >= this are kept: floor(float32(p) * 2^32),
+    at most 2^32 - 1 (the rule of the hvk_dropout* entries)."""
+    return max(0, min(0xFFFFFFFF, int(_f32(p) * 4294967296.0)))
+
+
 def dropout_mask_ref(n, seed, p, base=0):
     i = (torch.arange(n, dtype=torch.int64) + int(base)) & 0xFFFFFFFF
     h = _hash32(i, int(seed) & 0xFFFFFFFF)
-    thresh = min(0xFFFFFFFF, int(p * 4294967296.0))
-    return h >= thresh
+    return h >= dropout_thresh(p)
 
 
 def dropout(x, p, seed, out=None, seed_dev=None, base=0):
@@ -2138,8 +2149,13 @@ def dropout(x, p, seed, out=None, seed_dev=None, base=0):
                   x.numel(), int(seed) & 0xFFFFFFFF, float(p), None, _s(x))
         return out
     keep = dropout_mask_ref(x.numel(), seed, p, base).view(x.shape)
-    scale = 1.0 / (1.0 - p) if p < 1 else 0.0
-    out.copy_((x.float() * keep * scale).to(out.dtype))
+    # the float32 scale of the kernel entries; dropped elements are +0
+    one, p32 = torch.ones((), dtype=torch.float32), torch.tensor(
+        _f32(p), dtype=torch.float32)
+    scale = one / (one - p32) if p32 < 1 else torch.zeros(())
+    xf = x.float()
+    out.copy_(torch.where(keep, xf * scale, torch.zeros_like(xf))
+              .to(out.dtype))
     return out
 
 
