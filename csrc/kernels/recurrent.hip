@@ -464,3 +464,250 @@ HVK_API int hvk_recurrent_fn(int kind, const float* x, float* y, long long n,
                      x, y, n, kind);
   return (int)launch_status(s);
 }
+
+// ---------------------------------------------------------------- GRU
+// (docs/OPS.md "GRU").  Gate order r, z, n along the 3H axis:
+//   r = sigmoid(xg_r + h_prev . Whr^T),  z = sigmoid(xg_z + h_prev . Whz^T)
+//   hn = h_prev . Whn^T + b_hn,  n = tanh(xg_n + r hn)
+//   h = (1 - z) n + z h_prev
+// The reset gate multiplies the hidden-side product alone, so the step has
+// two gate gradients (input side dGx, hidden side dGh) and h is carried in
+// float32 (hf) next to the bf16 copy the MFMA reads.  Same tile, K split and
+// ordered reduction as above.
+namespace {
+
+struct GruFwdArgs {
+  const uint16_t* h_prev;   // [B][H] bf16, nullptr at step 0
+  const uint16_t* Wh;       // [3H][H] bf16
+  const float* xg;          // [B][3H] f32: x_t . Wx^T + (b_r, b_z, b_n)
+  const float* bhn;         // [H] f32 or nullptr: zeros
+  const float* hf_prev;     // [B][H] f32, nullptr: zeros
+  float* hf;                // [B][H] f32: h_t unrounded
+  float* hn;                // [B][H] f32
+  uint16_t* h;              // [B][H] bf16
+  uint16_t* gates;          // [B][3H] bf16 post-activation r z n, or nullptr
+  long long ld_hp, ld_w, ld_xg, ld_hfp, ld_hf, ld_hn, ld_h, ld_g;
+  int B, H;
+};
+
+template <bool VEC>
+__global__ void __launch_bounds__(NTHR) gru_fwd_kernel(const GruFwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * 3 * BSUB * WAVE];
+  const int j0 = blockIdx.x * TH, b0 = blockIdx.y * TB;
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const int B = a.B, H = a.H;
+  f32x4 sum[3];
+#pragma unroll
+  for (int g = 0; g < 3; ++g) sum[g] = f32x4{0, 0, 0, 0};
+  if (a.h_prev) {   // uniform over the grid
+    f32x4 acc[3][BSUB];
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+      for (int s = 0; s < BSUB; ++s) acc[g][s] = f32x4{0, 0, 0, 0};
+    product<3, VEC>(acc, a.Wh, a.ld_w, H, j0, a.h_prev, a.ld_hp, B, b0, H,
+                    lane, wid);
+    reduce<3>(acc, sum, red, lane, wid);
+  }
+  if (wid >= BSUB) return;
+  const int b = b0 + 16 * wid + (lane & 15);
+  const int j = j0 + 4 * (lane >> 4);
+  if (b >= B || j >= H) return;
+  const int n = min(4, H - j);   // VEC: H % 8 == 0, so n = 4
+  float pre[3][4], bh[4], hp[4], hnv[4], hv[4];
+#pragma unroll
+  for (int g = 0; g < 3; ++g)
+    ld4f<VEC>(a.xg + b * a.ld_xg + (long long)g * H + j, n, pre[g]);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) bh[r] = hp[r] = 0.f;
+  if (a.bhn) ld4f<VEC>(a.bhn + j, n, bh);
+  if (a.hf_prev) ld4f<VEC>(a.hf_prev + b * a.ld_hfp + j, n, hp);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float gr = sigm(pre[0][r] + sum[0][r]);
+    const float gz = sigm(pre[1][r] + sum[1][r]);
+    hnv[r] = sum[2][r] + bh[r];
+    const float gn = tanh_(fmaf(gr, hnv[r], pre[2][r]));
+    // z = 1 gives h_prev exactly, z = 0 gives n exactly
+    hv[r] = fmaf(gz, hp[r], (1.f - gz) * gn);
+    pre[0][r] = gr; pre[1][r] = gz; pre[2][r] = gn;
+  }
+  st4f<VEC>(a.hf + b * a.ld_hf + j, n, hv);
+  st4f<VEC>(a.hn + b * a.ld_hn + j, n, hnv);
+  st4h<VEC>(a.h + b * a.ld_h + j, n, hv);
+  if (a.gates) {
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+      st4h<VEC>(a.gates + b * a.ld_g + (long long)g * H + j, n, pre[g]);
+  }
+}
+
+struct GruBwdArgs {
+  const uint16_t* dgh_next; // [B][3H] bf16: dGh of step t + 1, or nullptr
+  const uint16_t* WhT;      // [H][3H] bf16: Wh transposed
+  const uint16_t* err;      // [B][H] bf16: error from above, or nullptr
+  const uint16_t* gates;    // [B][3H] bf16 saved r z n
+  const float* hn;          // [B][H] f32
+  const float* hf_prev;     // [B][H] f32 h_{t-1}, nullptr at t = 0
+  const float* dc_in;       // [B][H] f32 dh_{t+1} z_{t+1}, nullptr: zeros
+  float* dc_out;            // [B][H] f32 dh_t z_t
+  uint16_t* dgx;            // [B][3H] bf16 (dr, dz, dn)
+  uint16_t* dgh;            // [B][3H] bf16 (dr, dz, dn r)
+  long long ld_dgn, ld_wt, ld_e, ld_g, ld_hn, ld_hfp, ld_dci, ld_dco, ld_dgx,
+      ld_dgh;
+  int B, H;
+};
+
+template <bool VEC>
+__global__ void __launch_bounds__(NTHR) gru_bwd_kernel(const GruBwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * BSUB * WAVE];
+  const int j0 = blockIdx.x * TH, b0 = blockIdx.y * TB;
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const int B = a.B, H = a.H;
+  f32x4 sum[1] = {f32x4{0, 0, 0, 0}};
+  if (a.dgh_next) {   // uniform over the grid
+    f32x4 acc[1][BSUB];
+#pragma unroll
+    for (int s = 0; s < BSUB; ++s) acc[0][s] = f32x4{0, 0, 0, 0};
+    product<1, VEC>(acc, a.WhT, a.ld_wt, H, j0, a.dgh_next, a.ld_dgn, B, b0,
+                    3 * H, lane, wid);
+    reduce<1>(acc, sum, red, lane, wid);
+  }
+  if (wid >= BSUB) return;
+  const int b = b0 + 16 * wid + (lane & 15);
+  const int j = j0 + 4 * (lane >> 4);
+  if (b >= B || j >= H) return;
+  const int n = min(4, H - j);
+  float dh[4], gt[3][4], hnv[4], hp[4], dc[4], dx[3][4], dnr[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) dh[r] = hp[r] = dc[r] = 0.f;
+  if (a.err) ld4h<VEC>(a.err + b * a.ld_e + j, n, dh);
+  if (a.hf_prev) ld4f<VEC>(a.hf_prev + b * a.ld_hfp + j, n, hp);
+  if (a.dc_in) ld4f<VEC>(a.dc_in + b * a.ld_dci + j, n, dc);
+  ld4f<VEC>(a.hn + b * a.ld_hn + j, n, hnv);
+#pragma unroll
+  for (int g = 0; g < 3; ++g)
+    ld4h<VEC>(a.gates + b * a.ld_g + (long long)g * H + j, n, gt[g]);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float gr = gt[0][r], gz = gt[1][r], gn = gt[2][r];
+    const float d = dh[r] + sum[0][r] + dc[r];
+    const float dn = d * (1.f - gz) * (1.f - gn * gn);
+    dx[0][r] = dn * hnv[r] * gr * (1.f - gr);
+    dx[1][r] = d * (hp[r] - gn) * gz * (1.f - gz);
+    dx[2][r] = dn;
+    dnr[r] = dn * gr;
+    dc[r] = d * gz;
+  }
+  st4f<VEC>(a.dc_out + b * a.ld_dco + j, n, dc);
+#pragma unroll
+  for (int g = 0; g < 3; ++g)
+    st4h<VEC>(a.dgx + b * a.ld_dgx + (long long)g * H + j, n, dx[g]);
+  st4h<VEC>(a.dgh + b * a.ld_dgh + j, n, dx[0]);
+  st4h<VEC>(a.dgh + b * a.ld_dgh + (long long)H + j, n, dx[1]);
+  st4h<VEC>(a.dgh + b * a.ld_dgh + 2ll * H + j, n, dnr);
+}
+
+}  // namespace
+
+// One forward GRU time step (equations above).  h_prev nullptr: step 0, no
+// product, hn = b_hn.  hf_prev nullptr: zeros.  bhn nullptr: zeros.  gates
+// nullptr: not stored.  Every [B][.] operand has its own row pitch in
+// elements.
+HVK_API int hvk_gru_step_fwd(int B, int H, const void* h_prev,
+                             long long ld_hp, const void* Wh, long long ld_w,
+                             const float* xg, long long ld_xg,
+                             const float* hf_prev, long long ld_hfp,
+                             float* hf, long long ld_hf, float* hn,
+                             long long ld_hn, void* h, long long ld_h,
+                             void* gates, long long ld_g, const float* bhn,
+                             hipStream_t s) {
+  if (B < 1 || H < 1 || !xg || !h || !hf || !hn || (h_prev && !Wh)) return -1;
+  if (ld_xg < 3ll * H || ld_h < H || ld_hf < H || ld_hn < H ||
+      (h_prev && (ld_hp < H || ld_w < H)) || (hf_prev && ld_hfp < H) ||
+      (gates && ld_g < 3ll * H))
+    return -1;
+  GruFwdArgs a;
+  a.h_prev = (const uint16_t*)h_prev;
+  a.Wh = (const uint16_t*)Wh;
+  a.xg = xg;
+  a.bhn = bhn;
+  a.hf_prev = hf_prev;
+  a.hf = hf;
+  a.hn = hn;
+  a.h = (uint16_t*)h;
+  a.gates = (uint16_t*)gates;
+  a.ld_hp = ld_hp; a.ld_w = ld_w; a.ld_xg = ld_xg; a.ld_hfp = ld_hfp;
+  a.ld_hf = ld_hf; a.ld_hn = ld_hn; a.ld_h = ld_h; a.ld_g = ld_g;
+  a.B = B; a.H = H;
+  const bool vec = H % 8 == 0 && on_grid(xg, ld_xg) && on_grid(h, ld_h) &&
+                   on_grid(hf, ld_hf) && on_grid(hn, ld_hn) &&
+                   (!h_prev || (on_grid(h_prev, ld_hp) && on_grid(Wh, ld_w))) &&
+                   (!hf_prev || on_grid(hf_prev, ld_hfp)) &&
+                   (!bhn || on_grid(bhn, 8)) &&
+                   (!gates || on_grid(gates, ld_g));
+  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
+  if (grid.y > 65535u) return -1;
+  if (vec)
+    hipLaunchKernelGGL((gru_fwd_kernel<true>), grid, dim3(NTHR), 0, s, a);
+  else
+    hipLaunchKernelGGL((gru_fwd_kernel<false>), grid, dim3(NTHR), 0, s, a);
+  return (int)launch_status(s);
+}
+
+// One backward GRU time step from the saved gates (r, z, n), hn and the
+// float32 h_{t-1}:
+//   dh = err + dgh_next . Wh + dc_in            (each may be absent)
+//   dn = dh (1 - z)(1 - n^2),  dz = dh (h_prev - n) z(1 - z)
+//   dr = dn hn r(1 - r)
+//   dgx = (dr, dz, dn),  dgh = (dr, dz, dn r),  dc_out = dh z
+// WhT is [H][3H], Wh transposed.  dc_out may alias dc_in.
+HVK_API int hvk_gru_step_bwd(int B, int H, const void* dgh_next,
+                             long long ld_dgn, const void* WhT,
+                             long long ld_wt, const void* err, long long ld_e,
+                             const void* gates, long long ld_g,
+                             const float* hn, long long ld_hn,
+                             const float* hf_prev, long long ld_hfp,
+                             const float* dc_in, long long ld_dci,
+                             float* dc_out, long long ld_dco, void* dgx,
+                             long long ld_dgx, void* dgh, long long ld_dgh,
+                             hipStream_t s) {
+  if (B < 1 || H < 1 || !gates || !hn || !dc_out || !dgx || !dgh ||
+      (dgh_next && !WhT))
+    return -1;
+  const long long gh = 3ll * H;
+  if (ld_dgx < gh || ld_dgh < gh || ld_g < gh || ld_hn < H || ld_dco < H ||
+      (dgh_next && (ld_dgn < gh || ld_wt < gh)) || (err && ld_e < H) ||
+      (hf_prev && ld_hfp < H) || (dc_in && ld_dci < H))
+    return -1;
+  GruBwdArgs a;
+  a.dgh_next = (const uint16_t*)dgh_next;
+  a.WhT = (const uint16_t*)WhT;
+  a.err = (const uint16_t*)err;
+  a.gates = (const uint16_t*)gates;
+  a.hn = hn;
+  a.hf_prev = hf_prev;
+  a.dc_in = dc_in;
+  a.dc_out = dc_out;
+  a.dgx = (uint16_t*)dgx;
+  a.dgh = (uint16_t*)dgh;
+  a.ld_dgn = ld_dgn; a.ld_wt = ld_wt; a.ld_e = ld_e; a.ld_g = ld_g;
+  a.ld_hn = ld_hn; a.ld_hfp = ld_hfp; a.ld_dci = ld_dci; a.ld_dco = ld_dco;
+  a.ld_dgx = ld_dgx; a.ld_dgh = ld_dgh;
+  a.B = B; a.H = H;
+  const bool vec = H % 8 == 0 && on_grid(dgx, ld_dgx) && on_grid(dgh, ld_dgh) &&
+                   on_grid(gates, ld_g) && on_grid(hn, ld_hn) &&
+                   on_grid(dc_out, ld_dco) &&
+                   (!dgh_next ||
+                    (on_grid(dgh_next, ld_dgn) && on_grid(WhT, ld_wt))) &&
+                   (!err || on_grid(err, ld_e)) &&
+                   (!hf_prev || on_grid(hf_prev, ld_hfp)) &&
+                   (!dc_in || on_grid(dc_in, ld_dci));
+  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
+  if (grid.y > 65535u) return -1;
+  if (vec)
+    hipLaunchKernelGGL((gru_bwd_kernel<true>), grid, dim3(NTHR), 0, s, a);
+  else
+    hipLaunchKernelGGL((gru_bwd_kernel<false>), grid, dim3(NTHR), 0, s, a);
+  return (int)launch_status(s);
+}

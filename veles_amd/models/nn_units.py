@@ -106,9 +106,10 @@ class Forward(AcceleratedUnit):
         return ACTIVATION_MODES.get(self.activation, "ACTIVATION_LINEAR")
 
     # parameter plumbing ----------------------------------------------------
-    def register_params(self, wshape, fan_in):
+    def register_params(self, wshape, fan_in, bias_len=None):
         """Create (or restore) weights/bias on the host and register them in
-        the flat store."""
+        the flat store.  ``bias_len``: the bias length when it is not the
+        weights' row count (GRU: [3H] rows, [4H] bias)."""
         if self.weights.mem is None or self.weights.mem.shape != tuple(wshape):
             w = numpy.zeros(wshape, numpy.float32)
             std = self.weights_stddev
@@ -117,7 +118,7 @@ class Forward(AcceleratedUnit):
             fill_weights(w, self.weights_filling, std, self.rand)
             self.weights.reset(w)
         if self.include_bias:
-            n = wshape[0]
+            n = wshape[0] if bias_len is None else bias_len
             if self.bias.mem is None or self.bias.mem.shape != (n,):
                 b = numpy.zeros(n, numpy.float32)
                 std = self.bias_stddev

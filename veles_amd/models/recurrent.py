@@ -14,6 +14,15 @@ output is h_T (H,) or, with ``return_sequences``, every h_t (T, H).  The one
 the forget-gate bias is 1.  The forward is one GEMM for the input projection
 plus T fused step kernels (``ops.lstm_fwd``), the backward T step kernels
 plus three GEMMs (``ops.lstm_bwd``).
+
+GRU (pinned to torch.nn.GRU, parity unpinned): gate order r, z, n,
+
+    r, z = sigmoid(x_t.Wx^T + b + h_{t-1}.Wh^T)
+    hn = h_{t-1}.Whn^T + b_hn,  n = tanh(x_t.Wxn^T + b_n + r hn)
+    h_t = (1 - z) n + z h_{t-1}
+
+``weights`` [3H][I+H], ``bias`` [4H] = (b_r, b_z, b_n, b_hn), all filled
+uniformly with fan-in I + H; no forget bias (``ops.gru_fwd`` / ``gru_bwd``).
 """
 from __future__ import annotations
 
@@ -23,7 +32,7 @@ from veles_amd.models.nn_units import (
     Forward, GradientDescentBase, fill_weights)
 from veles_amd import ops
 
-__all__ = ["LSTM", "RNN", "GDLSTM", "GDRNN"]
+__all__ = ["LSTM", "RNN", "GRU", "GDLSTM", "GDRNN", "GDGRU"]
 
 
 class LSTM(Forward):
@@ -31,6 +40,7 @@ class LSTM(Forward):
     MAPPING = "lstm"
     CELL = "lstm"
     GATES = 4
+    BIAS_BLOCKS = 4   # bias length in units of H
 
     def __init__(self, workflow, **kwargs):
         super().__init__(workflow, **kwargs)
@@ -80,16 +90,17 @@ class LSTM(Forward):
                          std if self.weights_stddev is None
                          else self.weights_stddev, self.rand)
             self.weights.reset(w)
+        nb = self.BIAS_BLOCKS * H
         if self.include_bias and (self.bias.mem is None or
-                                  self.bias.mem.shape != (ng * H,)):
-            b = numpy.zeros(ng * H, numpy.float32)
+                                  self.bias.mem.shape != (nb,)):
+            b = numpy.zeros(nb, numpy.float32)
             fill_weights(b, self.bias_filling,
                          std if self.bias_stddev is None
                          else self.bias_stddev, self.rand)
             if ng == 4:
                 b[H:2 * H] = self.forget_bias
             self.bias.reset(b)
-        self.register_params(wshape, fan_in)
+        self.register_params(wshape, fan_in, bias_len=nb)
         self.save_ = {}
         y = self.alloc_output((B,) + self.output_sample_shape)
         if self.return_sequences:
@@ -104,12 +115,15 @@ class LSTM(Forward):
         seq = self.return_sequences
         testing = bool(getattr(self.workflow, "testing", False))
         out = None if seq else self.alloc_output((B, self.hidden))
-        y = ops.lstm_fwd(x, w, self.bias_master, self.hidden, cell=self.CELL,
-                         return_sequences=seq,
-                         save=None if testing else self.save_,
-                         ws=self.save_, out=out)
+        y = self.forward_op(x, w, return_sequences=seq,
+                            save=None if testing else self.save_,
+                            ws=self.save_, out=out)
         if seq:
             self.output.devmem = y
+
+    def forward_op(self, x, w, **kwargs):
+        return ops.lstm_fwd(x, w, self.bias_master, self.hidden,
+                            cell=self.CELL, **kwargs)
 
 
 class RNN(LSTM):
@@ -117,6 +131,18 @@ class RNN(LSTM):
     MAPPING = "rnn"
     CELL = "rnn"
     GATES = 1
+    BIAS_BLOCKS = 1
+
+
+class GRU(LSTM):
+    __id__ = "3c9e5b2a-6f14-4d8b-a7e0-8b1d4f6c2a95"
+    MAPPING = "gru"
+    CELL = "gru"
+    GATES = 3
+    BIAS_BLOCKS = 4   # (b_r, b_z, b_n, b_hn)
+
+    def forward_op(self, x, w, **kwargs):
+        return ops.gru_fwd(x, w, self.bias_master, self.hidden, **kwargs)
 
 
 class GDLSTM(GradientDescentBase):
@@ -148,12 +174,23 @@ class GDLSTM(GradientDescentBase):
         mode = "overwrite" if self.store_.overwrite else True
         ei = self.alloc_err_input(x.shape, w.dtype) \
             if self.need_err_input else None
-        ops.lstm_bwd(err, x, w, fwd.save_, pw.grad,
-                     None if pb is None else pb.grad, cell=fwd.CELL,
+        self.backward_op(err, x, w, fwd, pw.grad,
+                         None if pb is None else pb.grad, mode, ei)
+        self.report_gradients()
+
+    def backward_op(self, err, x, w, fwd, dw, dbias, mode, ei):
+        ops.lstm_bwd(err, x, w, fwd.save_, dw, dbias, cell=fwd.CELL,
                      accumulate=mode, need_err_input=self.need_err_input,
                      err_input=ei)
-        self.report_gradients()
 
 
 class GDRNN(GDLSTM):
     MAPPING = "rnn"
+
+
+class GDGRU(GDLSTM):
+    MAPPING = "gru"
+
+    def backward_op(self, err, x, w, fwd, dw, dbias, mode, ei):
+        ops.gru_bwd(err, x, w, fwd.save_, dw, dbias, accumulate=mode,
+                    need_err_input=self.need_err_input, err_input=ei)

@@ -50,7 +50,8 @@ from veles_amd.models.channel_splitting import (
     ChannelMerger, ChannelSplitter, GDChannelMerger, GDChannelSplitter)
 from veles_amd.models.cutter import Cutter, GDCutter
 from veles_amd.models.deconv import Deconv, GDDeconv
-from veles_amd.models.recurrent import GDLSTM, GDRNN, LSTM, RNN
+from veles_amd.models.recurrent import (
+    GDGRU, GDLSTM, GDRNN, GRU, LSTM, RNN)
 from veles_amd.models.rprop_all2all import RPropAll2All
 from veles_amd.models.standard_workflow_links import LinkBuilders
 from veles_amd.models.weights_zerofilling import GDZeroFiller, ZeroFiller
@@ -90,6 +91,7 @@ LAYER_TYPES = {
     "rprop_all2all": (All2All, RPropAll2All),
     "lstm": (LSTM, GDLSTM),
     "rnn": (RNN, GDRNN),
+    "gru": (GRU, GDGRU),
     "norm": (LRNormalizerForward, LRNormalizerBackward),
     "dropout": (DropoutForward, DropoutBackward),
     "activation_tanh": (act_units.ForwardTanh, act_units.BackwardTanh),

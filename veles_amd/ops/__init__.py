@@ -2845,6 +2845,297 @@ def lstm_bwd(err, x, w, save, dw, dbias, *, cell="lstm", accumulate="overwrite",
     return err_input
 
 
+# GRU (docs/OPS.md "GRU"): gate order r, z, n; the reset gate multiplies the
+# hidden-side product only, so it has step kernels and entry points of its own.
+def _gru_args(name, x, w, bias, H):
+    """Shared host checks of gru_fwd / gru_bwd; returns (B, T, I, H)."""
+    H = int(H)
+    if x.dim() != 3 or min(x.shape) < 1:
+        raise ValueError("%s: input must be [B][T][I], got %s" %
+                         (name, tuple(x.shape)))
+    B, T, I = x.shape
+    if H < 1 or w.dim() != 2 or tuple(w.shape) != (3 * H, I + H):
+        raise ValueError("%s: weights must be [%d][%d] (I = %d, H = %d), "
+                         "got %s" % (name, 3 * H, I + H, I, H,
+                                     tuple(w.shape)))
+    if x.device != w.device or (bias is not None and bias.device != w.device):
+        raise ValueError("%s: operands on different devices" % name)
+    if x.stride(2) != 1 or x.stride(0) != T * x.stride(1) or w.stride(1) != 1:
+        raise ValueError("%s: input rows must be contiguous with one pitch "
+                         "over [B][T], weight rows contiguous (strides %s, "
+                         "%s)" % (name, x.stride(), w.stride()))
+    if bias is not None and (tuple(bias.shape) != (4 * H,) or
+                             not bias.is_contiguous()):
+        raise ValueError("%s: bias must be a contiguous [%d] = (b_r, b_z, "
+                         "b_n, b_hn), got %s" %
+                         (name, 4 * H, tuple(bias.shape)))
+    if _gpu(w):
+        if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+            raise TypeError("%s: GPU input and weights must be bfloat16, got "
+                            "%s / %s" % (name, x.dtype, w.dtype))
+        if bias is not None and bias.dtype != torch.float32:
+            raise TypeError("%s: GPU bias must be float32, got %s" %
+                            (name, bias.dtype))
+        if x.data_ptr() % 2 or w.data_ptr() % 2:
+            raise ValueError("%s: operands off the element grid" % name)
+    elif not (x.is_floating_point() and w.is_floating_point()):
+        raise TypeError("%s: floating-point operands, got %s / %s" %
+                        (name, x.dtype, w.dtype))
+    if B * T * max(_r8(3 * H), x.stride(1)) >= 1 << 31:
+        raise ValueError("%s: %d x %d x %d exceeds 2^31 elements" %
+                         (name, B, T, max(3 * H, I)))
+    return B, T, I, H
+
+
+def gru_fwd(x, w, bias, H, *, return_sequences=False, save=None, out=None,
+            ws=None):
+    """Forward of a GRU layer over ``x`` [B][T][I] (batch-major).
+
+    ``w`` [3H][I+H] is ONE parameter: ``w[:, :I]`` is Wx, ``w[:, I:]`` is Wh,
+    gate order r, z, n; ``bias`` [4H] = (b_r, b_z, b_n, b_hn) or None (torch:
+    bias_ih = bias[:3H], bias_hh = (0, 0, bias[3H:])).  h starts at zero.
+
+        r = sigmoid(x_t.Wxr^T + b_r + h_{t-1}.Whr^T)
+        z = sigmoid(x_t.Wxz^T + b_z + h_{t-1}.Whz^T)
+        hn = h_{t-1}.Whn^T + b_hn,  n = tanh(x_t.Wxn^T + b_n + r hn)
+        h_t = (1 - z) n + z h_{t-1}
+
+    One GEMM projects all B*T rows with bias[:3H] (float32 ``xg``), then T
+    step launches run on the current stream with no host synchronisation
+    (capturable).  Returns h_T [B][H], or every h_t [B][T][H] with
+    ``return_sequences``.  ``save`` (a dict) receives "h" [B][T][H], "hf" (h
+    in float32: the carry z h_{t-1} is not rounded to bf16), "hn" float32,
+    "gates" [B][T][3H] (post-activation r, z, n) and "xg" for gru_bwd; with
+    ``save=None`` the gates are not written.  A kept ``save`` / ``ws`` dict
+    is reused: no allocation from the second call on."""
+    name = "gru_fwd"
+    B, T, I, H = _gru_args(name, x, w, bias, H)
+    dev = x.device
+    st = save if save is not None else (ws if ws is not None else {})
+    gh = 3 * H
+    if out is not None and not return_sequences and (
+            tuple(out.shape) != (B, H) or out.device != dev):
+        raise ValueError("%s: out must be [%d][%d] on %s" % (name, B, H, dev))
+    if _gpu(x):
+        fn = _rec_fn("hvk_gru_step_fwd")
+        P = _r8(gh)
+        xg_ = _rec_buf(st, "_xg", (B, T, P), torch.float32, dev)
+        h_all = _rec_buf(st, "h", (B, T, H), torch.bfloat16, dev)
+        hf = _rec_buf(st, "hf", (B, T, H), torch.float32, dev)
+        hn = _rec_buf(st, "hn", (B, T, H), torch.float32, dev)
+        g_ = _rec_buf(st, "_gates", (B, T, P), torch.bfloat16, dev) \
+            if save is not None else None
+        gemm(_rows(x, B, T), w[:, :I], trans_b=True,
+             bias=None if bias is None else bias[:gh],
+             out=xg_.view(B * T, P)[:, :gh])
+        stream = _s(x)
+        ph, phf, phn = h_all.data_ptr(), hf.data_ptr(), hn.data_ptr()
+        pxg, pg = xg_.data_ptr(), _p(g_)
+        pw, ldw = w.data_ptr() + 2 * I, w.stride(0)
+        pbh = None if bias is None else bias.data_ptr() + 4 * gh
+        for t in range(T):
+            rc = fn(B, H,
+                    ph + 2 * (t - 1) * H if t else None, T * H, pw, ldw,
+                    pxg + 4 * t * P, T * P,
+                    phf + 4 * (t - 1) * H if t else None, T * H,
+                    phf + 4 * t * H, T * H, phn + 4 * t * H, T * H,
+                    ph + 2 * t * H, T * H,
+                    pg + 2 * t * P if pg else None, T * P, pbh, stream)
+            if rc:
+                _lib.check(rc, "hvk_gru_step_fwd")
+        if save is not None:
+            save["xg"] = xg_[:, :, :gh]
+            save["gates"] = g_[:, :, :gh]
+    else:
+        xf, wf = x.float(), w.float()
+        xg = xf.reshape(B * T, I) @ wf[:, :I].t()
+        bhn = torch.zeros(H)
+        if bias is not None:
+            xg = xg + bias.float()[:gh].view(1, -1)
+            bhn = bias.float()[gh:]
+        xg = xg.view(B, T, gh)
+        wh = wf[:, I:]
+        h_all = _rec_buf(st, "h", (B, T, H), torch.float32, dev)
+        gs = save if save is not None else {}   # kept for a backward only
+        hn_all = _rec_buf(gs, "hn", (B, T, H), torch.float32, dev)
+        gates = _rec_buf(gs, "gates", (B, T, gh), torch.float32, dev)
+        h = torch.zeros(B, H)
+        for t in range(T):
+            hh = h @ wh.t() if t else torch.zeros(B, gh)
+            gr = torch.sigmoid(xg[:, t, :H] + hh[:, :H])
+            gz = torch.sigmoid(xg[:, t, H:2 * H] + hh[:, H:2 * H])
+            hn = hh[:, 2 * H:] + bhn
+            gn = torch.tanh(xg[:, t, 2 * H:] + gr * hn)
+            h = (1.0 - gz) * gn + gz * h
+            h_all[:, t] = h
+            hn_all[:, t] = hn
+            gates[:, t] = torch.cat((gr, gz, gn), 1)
+        st["hf"] = h_all    # float32 already: one tensor serves both
+        if save is not None:
+            save["xg"] = xg
+    if return_sequences:
+        return h_all
+    last = h_all[:, T - 1]
+    if out is None:
+        return last.contiguous()
+    out.copy_(last)
+    return out
+
+
+def gru_bwd(err, x, w, save, dw, dbias, *, accumulate="overwrite",
+            need_err_input=True, err_input=None):
+    """Backward of gru_fwd from its ``save`` dict.
+
+    ``err`` is dL/dh_T [B][H], or dL/dh_t for every step [B][T][H] (the
+    layer ran with ``return_sequences``).  T step launches (t = T-1 .. 0):
+
+        dh = err_t + dGh_{t+1}.Wh + dcarry_{t+1}
+        dn = dh (1 - z)(1 - n^2),  dz = dh (h_{t-1} - n) z(1 - z)
+        dr = dn hn r(1 - r)
+        dGx_t = (dr, dz, dn),  dGh_t = (dr, dz, dn r),  dcarry_t = dh z
+
+    fill save["dgx"] and save["dgh"] (two [B][T][3H] buffers: the gradient of
+    the input-side and of the hidden-side pre-activations) and
+    save["dcarry"] [T][B][H] float32; then ``dw[:, :I]`` (+)= dGx^T.X with
+    ``dbias[:3H]`` (+)= its column sums, ``dw[:, I:]`` (+)= dGh^T.H_prev with
+    ``dbias[3H:]`` (+)= the column sums of dGh[:, 2H:3H] (``accumulate``: True
+    adds, "overwrite" writes, as in ``gemm``), and, with ``need_err_input``,
+    err_input [B][T][I] = dGx.Wx is returned.  ``dw`` is float32 [3H][I+H],
+    ``dbias`` float32 [4H] or None.  Bit-reproducible under
+    ``set_deterministic(True)``."""
+    name = "gru_bwd"
+    if w.dim() != 2 or w.shape[0] % 3:
+        raise ValueError("%s: weights %s" % (name, tuple(w.shape)))
+    B, T, I, H = _gru_args(name, x, w, None, w.shape[0] // 3)
+    dev = x.device
+    gh = 3 * H
+    if accumulate not in (True, "overwrite"):
+        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
+                         name)
+    seq = err.dim() == 3
+    if tuple(err.shape) != ((B, T, H) if seq else (B, H)) or \
+            err.stride(-1) != 1 or err.device != dev:
+        raise ValueError("%s: err must be [%d][%d] or [%d][%d][%d] with "
+                         "contiguous rows on %s, got %s" %
+                         (name, B, H, B, T, H, dev, tuple(err.shape)))
+    if dw.dtype != torch.float32 or tuple(dw.shape) != (gh, I + H) or \
+            dw.stride(1) != 1 or dw.device != dev:
+        raise ValueError("%s: dw must be float32 [%d][%d] on %s" %
+                         (name, gh, I + H, dev))
+    if dbias is not None and (dbias.dtype != torch.float32 or
+                              tuple(dbias.shape) != (4 * H,) or
+                              not dbias.is_contiguous() or
+                              dbias.device != dev):
+        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
+                         % (name, 4 * H, dev))
+    hdt = torch.bfloat16 if _gpu(x) else torch.float32
+    for k, shape, dt in (("h", (B, T, H), hdt),
+                         ("hf", (B, T, H), torch.float32),
+                         ("hn", (B, T, H), torch.float32),
+                         ("gates", (B, T, gh), hdt)):
+        t = None if save is None else save.get(k)
+        if t is None or tuple(t.shape) != shape or t.dtype != dt or \
+                t.device != dev:
+            raise ValueError("%s: save[%r] must be %s %s from gru_fwd" %
+                             (name, k, dt, shape))
+    if need_err_input and err_input is not None and (
+            tuple(err_input.shape) != (B, T, I) or
+            not err_input.is_contiguous() or err_input.device != dev or
+            err_input.dtype != hdt):
+        raise ValueError("%s: err_input must be a contiguous %s [%d][%d][%d]"
+                         % (name, hdt, B, T, I))
+    h_all = save["h"]
+    if _gpu(x):
+        if err.dtype != torch.bfloat16:
+            raise TypeError("%s: GPU err must be bfloat16, got %s" %
+                            (name, err.dtype))
+        fn = _rec_fn("hvk_gru_step_bwd")
+        P = _r8(gh)
+        g_ = save.get("_gates")
+        if g_ is None or tuple(g_.shape) != (B, T, P) or \
+                g_.data_ptr() != save["gates"].data_ptr():
+            raise ValueError("%s: save[\"gates\"] is not gru_fwd's" % name)
+        # Wh^T, one copy per call: the product of a step sums over Wh's rows
+        wt = _rec_buf(save, "_wht", (H, P), torch.bfloat16, dev)
+        wt[:, :gh].copy_(w[:, I:].t())
+        dgx_ = _rec_buf(save, "_dgx", (B, T, P), torch.bfloat16, dev,
+                        zero=True)
+        dgh_ = _rec_buf(save, "_dgh", (B, T, P), torch.bfloat16, dev,
+                        zero=True)
+        # dcarry[t] = dh_t z_t as step t leaves it (read by step t - 1)
+        dc = _rec_buf(save, "dcarry", (T, B, H), torch.float32, dev)
+        stream = _s(x)
+        pdx, pdh, pwt = dgx_.data_ptr(), dgh_.data_ptr(), wt.data_ptr()
+        pdc, pgt = dc.data_ptr(), g_.data_ptr()
+        phn, phf = save["hn"].data_ptr(), save["hf"].data_ptr()
+        pe = err.data_ptr()
+        lde = err.stride(0)
+        for t in range(T - 1, -1, -1):
+            last = t == T - 1
+            rc = fn(B, H,
+                    None if last else pdh + 2 * (t + 1) * P, T * P, pwt, P,
+                    pe + 2 * t * err.stride(1) if seq else
+                    (pe if last else None), lde,
+                    pgt + 2 * t * P, T * P, phn + 4 * t * H, T * H,
+                    phf + 4 * (t - 1) * H if t else None, T * H,
+                    None if last else pdc + 4 * (t + 1) * B * H, H,
+                    pdc + 4 * t * B * H, H,
+                    pdx + 2 * t * P, T * P, pdh + 2 * t * P, T * P, stream)
+            if rc:
+                _lib.check(rc, "hvk_gru_step_bwd")
+        dgx, dgh = dgx_[:, :, :gh], dgh_[:, :, :gh]
+        dgx2 = dgx_.view(B * T, P)[:, :gh]
+        dgh2 = dgh_.view(B * T, P)[:, :gh]
+    else:
+        wh = w.float()[:, I:]
+        dgx = _rec_buf(save, "dgx", (B, T, gh), torch.float32, dev)
+        dgh = _rec_buf(save, "dgh", (B, T, gh), torch.float32, dev)
+        dc = _rec_buf(save, "dcarry", (T, B, H), torch.float32, dev)
+        ef = err.float()
+        zero = torch.zeros(B, H)
+        for t in range(T - 1, -1, -1):
+            dh = ef[:, t] if seq else (ef if t == T - 1 else zero)
+            if t < T - 1:
+                dh = dh + dgh[:, t + 1] @ wh + dc[t + 1]
+            gr, gz, gn = save["gates"][:, t].float().split(H, 1)
+            hp = save["hf"][:, t - 1] if t else zero
+            dn = dh * (1.0 - gz) * (1.0 - gn * gn)
+            dz = dh * (hp - gn) * gz * (1.0 - gz)
+            dr = dn * save["hn"][:, t] * gr * (1.0 - gr)
+            dgx[:, t] = torch.cat((dr, dz, dn), 1)
+            dgh[:, t] = torch.cat((dr, dz, dn * gr), 1)
+            dc[t] = dh * gz
+        dgx2, dgh2 = dgx.view(B * T, gh), dgh.view(B * T, gh)
+    save["dgx"], save["dgh"] = dgx, dgh
+    # h_{t-1} of every row: h shifted by one step, zeros at t = 0
+    hp = _rec_buf(save, "_hprev", (B, T, H), hdt, dev, zero=True)
+    if T > 1:
+        hp[:, 1:].copy_(h_all[:, :T - 1])
+    gemm(dgx2, _rows(x, B, T), trans_a=True, out=dw[:, :I],
+         accumulate=accumulate,
+         bias_grad=None if dbias is None else dbias[:gh])
+    # the ones column of the hidden-side GEMM sums every column of dGh; its
+    # n block is the gradient of b_hn
+    sums = None
+    if dbias is not None:
+        sums = _rec_buf(save, "_dbh", (gh,), torch.float32, dev)
+        if accumulate is True:
+            sums.zero_()
+    gemm(dgh2, hp.view(B * T, H), trans_a=True, out=dw[:, I:],
+         accumulate=accumulate, bias_grad=sums)
+    if dbias is not None:
+        if accumulate is True:
+            dbias[gh:] += sums[2 * H:]
+        else:
+            dbias[gh:].copy_(sums[2 * H:])
+    if not need_err_input:
+        return None
+    if err_input is None:
+        err_input = torch.empty(B, T, I, dtype=hdt, device=dev)
+    gemm(dgx2, w[:, :I], out=err_input.view(B * T, I))
+    return err_input
+
+
 # ------------------------------------------- restricted Boltzmann machines
 # docs/OPS.md "Restricted Boltzmann machines"; kernels in csrc/kernels/rbm.hip.
 def _rbm_fn(name):

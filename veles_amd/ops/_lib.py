@@ -149,6 +149,11 @@ _OPTIONAL = {
     "hvk_lstm_step_fwd": [I, I, I] + [P, L] * 7 + [P],
     "hvk_lstm_step_bwd": [I, I, I] + [P, L] * 9 + [P],
     "hvk_recurrent_fn": [I, P, P, L, P],
+    # GRU: (B, H, h_prev, Wh, xg, hf_prev, hf, hn, h, gates, b_hn, s) and
+    # (B, H, dgh_next, WhT, err, gates, hn, hf_prev, dc_in, dc_out, dgx, dgh,
+    # s), every [B][.] operand followed by its row pitch
+    "hvk_gru_step_fwd": [I, I] + [P, L] * 8 + [P, P],
+    "hvk_gru_step_bwd": [I, I] + [P, L] * 10 + [P],
     # restricted Boltzmann machines (csrc/kernels/rbm.hip): (transposed, n,
     # V, H, x, ldx, w, ldw, bias, probs, ldp, sample, lds, seed, seed_dev,
     # base, s); (n, V, H, splits); (n, V, H, v0, h0, vk, hk each with its
