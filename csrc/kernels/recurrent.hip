@@ -6,7 +6,10 @@
 //   hvk_lstm_step_bwd  acc[B][H] = dG_next . Wh (from a transposed copy of
 //                      Wh) with the cell's backward in the epilogue.
 // One launch is one time step; the stream orders the steps.  No kernel waits
-// for another workgroup, nothing is atomic.
+// for another workgroup, nothing is atomic.  The ...2 entry points advance the
+// two independent chains of a bidirectional layer in ONE launch: grid.z is the
+// direction, a workgroup picks its direction's argument block and runs the
+// same body as the one-direction kernel (docs/OPS.md "Bidirectional").
 //
 // Tile: a workgroup owns 16 hidden units x 32 batch rows and, forward, all
 // NG gates of those units (NG = 4 LSTM, gate order i f g o; NG = 1 RNN).
@@ -184,6 +187,13 @@ __device__ __forceinline__ void st4h(uint16_t* p, int n, const float* v) {
   }
 }
 
+// the argument blocks of a paired launch, indexed by blockIdx.z (a scalar
+// offset into the kernel arguments: no vector registers)
+template <class A>
+struct Pair {
+  A d[2];
+};
+
 struct FwdArgs {
   const uint16_t* h_prev;   // [B][H] bf16, nullptr at step 0
   const uint16_t* Wh;       // [NG*H][H] bf16
@@ -197,15 +207,14 @@ struct FwdArgs {
 };
 
 template <int NG, bool VEC>
-__global__ void __launch_bounds__(NTHR) step_fwd_kernel(const FwdArgs a) {
-  __shared__ __attribute__((aligned(16))) float4 red[NW * NG * BSUB * WAVE];
+__device__ __forceinline__ void step_fwd_body(const FwdArgs& a, float4* red) {
   const int j0 = blockIdx.x * TH, b0 = blockIdx.y * TB;
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int B = a.B, H = a.H;
   f32x4 sum[NG];
 #pragma unroll
   for (int g = 0; g < NG; ++g) sum[g] = f32x4{0, 0, 0, 0};
-  if (a.h_prev) {   // uniform over the grid
+  if (a.h_prev) {   // uniform over the workgroup's direction
     f32x4 acc[NG][BSUB];
 #pragma unroll
     for (int g = 0; g < NG; ++g)
@@ -255,6 +264,20 @@ __global__ void __launch_bounds__(NTHR) step_fwd_kernel(const FwdArgs a) {
   st4h<VEC>(a.h + b * a.ld_h + j, n, hv);
 }
 
+template <int NG, bool VEC>
+__global__ void __launch_bounds__(NTHR) step_fwd_kernel(const FwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * NG * BSUB * WAVE];
+  step_fwd_body<NG, VEC>(a, red);
+}
+
+// both directions in one launch: blockIdx.z indexes the argument blocks
+template <int NG, bool VEC>
+__global__ void __launch_bounds__(NTHR)
+step_fwd2_kernel(const Pair<FwdArgs> p) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * NG * BSUB * WAVE];
+  step_fwd_body<NG, VEC>(p.d[blockIdx.z], red);
+}
+
 struct BwdArgs {
   const uint16_t* dg_next;  // [B][NG*H] bf16: dG of step t + 1, or nullptr
   const uint16_t* WhT;      // [H][NG*H] bf16: Wh transposed
@@ -270,13 +293,12 @@ struct BwdArgs {
 };
 
 template <int NG, bool VEC>
-__global__ void __launch_bounds__(NTHR) step_bwd_kernel(const BwdArgs a) {
-  __shared__ __attribute__((aligned(16))) float4 red[NW * BSUB * WAVE];
+__device__ __forceinline__ void step_bwd_body(const BwdArgs& a, float4* red) {
   const int j0 = blockIdx.x * TH, b0 = blockIdx.y * TB;
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int B = a.B, H = a.H;
   f32x4 sum[1] = {f32x4{0, 0, 0, 0}};
-  if (a.dg_next) {   // uniform over the grid
+  if (a.dg_next) {   // uniform over the workgroup's direction
     f32x4 acc[1][BSUB];
 #pragma unroll
     for (int s = 0; s < BSUB; ++s) acc[0][s] = f32x4{0, 0, 0, 0};
@@ -327,6 +349,20 @@ __global__ void __launch_bounds__(NTHR) step_bwd_kernel(const BwdArgs a) {
     st4h<VEC>(a.dg + b * a.ld_dg + (long long)g * H + j, n, d[g]);
 }
 
+template <int NG, bool VEC>
+__global__ void __launch_bounds__(NTHR) step_bwd_kernel(const BwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * BSUB * WAVE];
+  step_bwd_body<NG, VEC>(a, red);
+}
+
+// both directions in one launch: blockIdx.z indexes the argument blocks
+template <int NG, bool VEC>
+__global__ void __launch_bounds__(NTHR)
+step_bwd2_kernel(const Pair<BwdArgs> p) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * BSUB * WAVE];
+  step_bwd_body<NG, VEC>(p.d[blockIdx.z], red);
+}
+
 // y[i] = the cell's own logistic function (kind 0) / tanh (kind 1) of x[i]:
 // lets a test measure the device functions the epilogues use
 __global__ void __launch_bounds__(NTHR)
@@ -349,22 +385,24 @@ inline bool on_grid(const void* p, long long ld) {
 // unused.  h_prev nullptr: step 0, no product.  c_prev nullptr: zeros.  gates
 // nullptr: not stored.  Every operand has its own row pitch in elements, so a
 // step of a batch-major [B][T][.] tensor is a strided view.
-HVK_API int hvk_lstm_step_fwd(int cell, int B, int H, const void* h_prev,
-                              long long ld_hp, const void* Wh, long long ld_w,
-                              const float* xg, long long ld_xg,
-                              const float* c_prev, long long ld_cp, float* c,
-                              long long ld_c, void* h, long long ld_h,
-                              void* gates, long long ld_g, hipStream_t s) {
+namespace {
+
+// Checks one direction's operands and fills its argument block; false:
+// refuse.  vec: every operand on the 16-B grid.
+bool fwd_args(FwdArgs& a, bool& vec, int cell, int B, int H,
+              const void* h_prev, long long ld_hp, const void* Wh,
+              long long ld_w, const float* xg, long long ld_xg,
+              const float* c_prev, long long ld_cp, float* c, long long ld_c,
+              void* h, long long ld_h, void* gates, long long ld_g) {
   const bool lstm = cell == CELL_LSTM;
   if ((cell != CELL_LSTM && cell != CELL_RNN) || B < 1 || H < 1 || !xg ||
       !h || (h_prev && !Wh) || (lstm && !c))
-    return -1;
+    return false;
   const int ng = lstm ? 4 : 1;
   if (ld_xg < (long long)ng * H || ld_h < H || (h_prev && ld_hp < H) ||
       (h_prev && ld_w < H) || (lstm && ld_c < H) ||
       (lstm && c_prev && ld_cp < H) || (lstm && gates && ld_g < 4ll * H))
-    return -1;
-  FwdArgs a;
+    return false;
   a.h_prev = (const uint16_t*)h_prev;
   a.Wh = (const uint16_t*)Wh;
   a.xg = xg;
@@ -375,11 +413,28 @@ HVK_API int hvk_lstm_step_fwd(int cell, int B, int H, const void* h_prev,
   a.ld_hp = ld_hp; a.ld_w = ld_w; a.ld_xg = ld_xg; a.ld_cp = ld_cp;
   a.ld_c = ld_c; a.ld_h = ld_h; a.ld_g = ld_g;
   a.B = B; a.H = H;
-  const bool vec = H % 8 == 0 && on_grid(xg, ld_xg) && on_grid(h, ld_h) &&
-                   (!h_prev || (on_grid(h_prev, ld_hp) && on_grid(Wh, ld_w))) &&
-                   (!lstm || on_grid(c, ld_c)) &&
-                   (!a.c_prev || on_grid(c_prev, ld_cp)) &&
-                   (!a.gates || on_grid(gates, ld_g));
+  vec = H % 8 == 0 && on_grid(xg, ld_xg) && on_grid(h, ld_h) &&
+        (!h_prev || (on_grid(h_prev, ld_hp) && on_grid(Wh, ld_w))) &&
+        (!lstm || on_grid(c, ld_c)) &&
+        (!a.c_prev || on_grid(c_prev, ld_cp)) &&
+        (!a.gates || on_grid(gates, ld_g));
+  return true;
+}
+
+}  // namespace
+
+HVK_API int hvk_lstm_step_fwd(int cell, int B, int H, const void* h_prev,
+                              long long ld_hp, const void* Wh, long long ld_w,
+                              const float* xg, long long ld_xg,
+                              const float* c_prev, long long ld_cp, float* c,
+                              long long ld_c, void* h, long long ld_h,
+                              void* gates, long long ld_g, hipStream_t s) {
+  FwdArgs a;
+  bool vec;
+  if (!fwd_args(a, vec, cell, B, H, h_prev, ld_hp, Wh, ld_w, xg, ld_xg,
+                c_prev, ld_cp, c, ld_c, h, ld_h, gates, ld_g))
+    return -1;
+  const bool lstm = cell == CELL_LSTM;
   const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
   if (grid.y > 65535u) return -1;
 #define HVK_REC_FWD(NG, VEC) \
@@ -395,32 +450,72 @@ HVK_API int hvk_lstm_step_fwd(int cell, int B, int H, const void* h_prev,
   return (int)launch_status(s);
 }
 
+// One forward time step of BOTH directions of a bidirectional layer in one
+// launch (grid.z = 2): the operand list of hvk_lstm_step_fwd once per
+// direction (0: forward chain, 1: reverse chain; each at its own time step).
+// Per direction the launch does exactly what hvk_lstm_step_fwd does, bit for
+// bit; null operands are per direction.  The vector path needs every operand
+// of both directions on the 16-B grid.
+HVK_API int hvk_lstm_step_fwd2(
+    int cell, int B, int H, const void* h_prev0, long long ld_hp0,
+    const void* Wh0, long long ld_w0, const float* xg0, long long ld_xg0,
+    const float* c_prev0, long long ld_cp0, float* c0, long long ld_c0,
+    void* h0, long long ld_h0, void* gates0, long long ld_g0,
+    const void* h_prev1, long long ld_hp1, const void* Wh1, long long ld_w1,
+    const float* xg1, long long ld_xg1, const float* c_prev1,
+    long long ld_cp1, float* c1, long long ld_c1, void* h1, long long ld_h1,
+    void* gates1, long long ld_g1, hipStream_t s) {
+  Pair<FwdArgs> p;
+  FwdArgs &a0 = p.d[0], &a1 = p.d[1];
+  bool vec0, vec1;
+  if (!fwd_args(a0, vec0, cell, B, H, h_prev0, ld_hp0, Wh0, ld_w0, xg0,
+                ld_xg0, c_prev0, ld_cp0, c0, ld_c0, h0, ld_h0, gates0,
+                ld_g0) ||
+      !fwd_args(a1, vec1, cell, B, H, h_prev1, ld_hp1, Wh1, ld_w1, xg1,
+                ld_xg1, c_prev1, ld_cp1, c1, ld_c1, h1, ld_h1, gates1, ld_g1))
+    return -1;
+  const bool lstm = cell == CELL_LSTM, vec = vec0 && vec1;
+  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB),
+                  2);
+  if (grid.y > 65535u) return -1;
+#define HVK_REC_FWD2(NG, VEC)                                                \
+  hipLaunchKernelGGL((step_fwd2_kernel<NG, VEC>), grid, dim3(NTHR), 0, s, p)
+  if (lstm) {
+    if (vec) HVK_REC_FWD2(4, true);
+    else HVK_REC_FWD2(4, false);
+  } else {
+    if (vec) HVK_REC_FWD2(1, true);
+    else HVK_REC_FWD2(1, false);
+  }
+#undef HVK_REC_FWD2
+  return (int)launch_status(s);
+}
+
 // One backward time step: dh = err + dg_next . Wh (either may be absent),
 // then, LSTM, from the saved gates, c_prev, c and the carried dc_in:
 //   dc = dc_in + dh o (1 - tanh(c)^2)
 //   dG = (dc g i(1-i), dc c_prev f(1-f), dc i (1-g^2), dh tanh(c) o(1-o))
 //   dc_out = dc f
 // RNN (gates = h_t): dG = dh (1 - h^2).  WhT is [H][NG*H], Wh transposed.
-HVK_API int hvk_lstm_step_bwd(int cell, int B, int H, const void* dg_next,
-                              long long ld_dgn, const void* WhT,
-                              long long ld_wt, const void* err,
-                              long long ld_e, const void* gates,
-                              long long ld_g, const float* c_prev,
-                              long long ld_cp, const float* c, long long ld_c,
-                              const float* dc_in, long long ld_dci,
-                              float* dc_out, long long ld_dco, void* dg,
-                              long long ld_dg, hipStream_t s) {
+namespace {
+
+bool bwd_args(BwdArgs& a, bool& vec, int cell, int B, int H,
+              const void* dg_next, long long ld_dgn, const void* WhT,
+              long long ld_wt, const void* err, long long ld_e,
+              const void* gates, long long ld_g, const float* c_prev,
+              long long ld_cp, const float* c, long long ld_c,
+              const float* dc_in, long long ld_dci, float* dc_out,
+              long long ld_dco, void* dg, long long ld_dg) {
   const bool lstm = cell == CELL_LSTM;
   if ((cell != CELL_LSTM && cell != CELL_RNN) || B < 1 || H < 1 || !gates ||
       !dg || (dg_next && !WhT) || (lstm && (!c || !dc_out)))
-    return -1;
+    return false;
   const long long gh = (lstm ? 4ll : 1ll) * H;
   if (ld_dg < gh || ld_g < gh || (dg_next && (ld_dgn < gh || ld_wt < gh)) ||
       (err && ld_e < H) ||
       (lstm && (ld_c < H || ld_dco < H || (c_prev && ld_cp < H) ||
                 (dc_in && ld_dci < H))))
-    return -1;
-  BwdArgs a;
+    return false;
   a.dg_next = (const uint16_t*)dg_next;
   a.WhT = (const uint16_t*)WhT;
   a.err = (const uint16_t*)err;
@@ -434,13 +529,33 @@ HVK_API int hvk_lstm_step_bwd(int cell, int B, int H, const void* dg_next,
   a.ld_cp = ld_cp; a.ld_c = ld_c; a.ld_dci = ld_dci; a.ld_dco = ld_dco;
   a.ld_dg = ld_dg;
   a.B = B; a.H = H;
-  const bool vec = H % 8 == 0 && on_grid(dg, ld_dg) && on_grid(gates, ld_g) &&
-                   (!dg_next ||
-                    (on_grid(dg_next, ld_dgn) && on_grid(WhT, ld_wt))) &&
-                   (!err || on_grid(err, ld_e)) &&
-                   (!lstm || (on_grid(c, ld_c) && on_grid(dc_out, ld_dco))) &&
-                   (!a.c_prev || on_grid(c_prev, ld_cp)) &&
-                   (!a.dc_in || on_grid(dc_in, ld_dci));
+  vec = H % 8 == 0 && on_grid(dg, ld_dg) && on_grid(gates, ld_g) &&
+        (!dg_next || (on_grid(dg_next, ld_dgn) && on_grid(WhT, ld_wt))) &&
+        (!err || on_grid(err, ld_e)) &&
+        (!lstm || (on_grid(c, ld_c) && on_grid(dc_out, ld_dco))) &&
+        (!a.c_prev || on_grid(c_prev, ld_cp)) &&
+        (!a.dc_in || on_grid(dc_in, ld_dci));
+  return true;
+}
+
+}  // namespace
+
+HVK_API int hvk_lstm_step_bwd(int cell, int B, int H, const void* dg_next,
+                              long long ld_dgn, const void* WhT,
+                              long long ld_wt, const void* err,
+                              long long ld_e, const void* gates,
+                              long long ld_g, const float* c_prev,
+                              long long ld_cp, const float* c, long long ld_c,
+                              const float* dc_in, long long ld_dci,
+                              float* dc_out, long long ld_dco, void* dg,
+                              long long ld_dg, hipStream_t s) {
+  BwdArgs a;
+  bool vec;
+  if (!bwd_args(a, vec, cell, B, H, dg_next, ld_dgn, WhT, ld_wt, err, ld_e,
+                gates, ld_g, c_prev, ld_cp, c, ld_c, dc_in, ld_dci, dc_out,
+                ld_dco, dg, ld_dg))
+    return -1;
+  const bool lstm = cell == CELL_LSTM;
   const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
   if (grid.y > 65535u) return -1;
 #define HVK_REC_BWD(NG, VEC) \
@@ -453,6 +568,48 @@ HVK_API int hvk_lstm_step_bwd(int cell, int B, int H, const void* dg_next,
     else HVK_REC_BWD(1, false);
   }
 #undef HVK_REC_BWD
+  return (int)launch_status(s);
+}
+
+// One backward time step of both directions in one launch (grid.z = 2): the
+// operand list of hvk_lstm_step_bwd once per direction, null operands per
+// direction, bit for bit what hvk_lstm_step_bwd does on either.
+HVK_API int hvk_lstm_step_bwd2(
+    int cell, int B, int H, const void* dg_next0, long long ld_dgn0,
+    const void* WhT0, long long ld_wt0, const void* err0, long long ld_e0,
+    const void* gates0, long long ld_g0, const float* c_prev0,
+    long long ld_cp0, const float* c0, long long ld_c0, const float* dc_in0,
+    long long ld_dci0, float* dc_out0, long long ld_dco0, void* dg0,
+    long long ld_dg0, const void* dg_next1, long long ld_dgn1,
+    const void* WhT1, long long ld_wt1, const void* err1, long long ld_e1,
+    const void* gates1, long long ld_g1, const float* c_prev1,
+    long long ld_cp1, const float* c1, long long ld_c1, const float* dc_in1,
+    long long ld_dci1, float* dc_out1, long long ld_dco1, void* dg1,
+    long long ld_dg1, hipStream_t s) {
+  Pair<BwdArgs> p;
+  BwdArgs &a0 = p.d[0], &a1 = p.d[1];
+  bool vec0, vec1;
+  if (!bwd_args(a0, vec0, cell, B, H, dg_next0, ld_dgn0, WhT0, ld_wt0, err0,
+                ld_e0, gates0, ld_g0, c_prev0, ld_cp0, c0, ld_c0, dc_in0,
+                ld_dci0, dc_out0, ld_dco0, dg0, ld_dg0) ||
+      !bwd_args(a1, vec1, cell, B, H, dg_next1, ld_dgn1, WhT1, ld_wt1, err1,
+                ld_e1, gates1, ld_g1, c_prev1, ld_cp1, c1, ld_c1, dc_in1,
+                ld_dci1, dc_out1, ld_dco1, dg1, ld_dg1))
+    return -1;
+  const bool lstm = cell == CELL_LSTM, vec = vec0 && vec1;
+  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB),
+                  2);
+  if (grid.y > 65535u) return -1;
+#define HVK_REC_BWD2(NG, VEC)                                                \
+  hipLaunchKernelGGL((step_bwd2_kernel<NG, VEC>), grid, dim3(NTHR), 0, s, p)
+  if (lstm) {
+    if (vec) HVK_REC_BWD2(4, true);
+    else HVK_REC_BWD2(4, false);
+  } else {
+    if (vec) HVK_REC_BWD2(1, true);
+    else HVK_REC_BWD2(1, false);
+  }
+#undef HVK_REC_BWD2
   return (int)launch_status(s);
 }
 
@@ -491,15 +648,14 @@ struct GruFwdArgs {
 };
 
 template <bool VEC>
-__global__ void __launch_bounds__(NTHR) gru_fwd_kernel(const GruFwdArgs a) {
-  __shared__ __attribute__((aligned(16))) float4 red[NW * 3 * BSUB * WAVE];
+__device__ __forceinline__ void gru_fwd_body(const GruFwdArgs& a, float4* red) {
   const int j0 = blockIdx.x * TH, b0 = blockIdx.y * TB;
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int B = a.B, H = a.H;
   f32x4 sum[3];
 #pragma unroll
   for (int g = 0; g < 3; ++g) sum[g] = f32x4{0, 0, 0, 0};
-  if (a.h_prev) {   // uniform over the grid
+  if (a.h_prev) {   // uniform over the workgroup's direction
     f32x4 acc[3][BSUB];
 #pragma unroll
     for (int g = 0; g < 3; ++g)
@@ -509,10 +665,9 @@ __global__ void __launch_bounds__(NTHR) gru_fwd_kernel(const GruFwdArgs a) {
                     lane, wid);
     reduce<3>(acc, sum, red, lane, wid);
   }
-  if (wid >= BSUB) return;
   const int b = b0 + 16 * wid + (lane & 15);
   const int j = j0 + 4 * (lane >> 4);
-  if (b >= B || j >= H) return;
+  if (wid >= BSUB || b >= B || j >= H) return;
   const int n = min(4, H - j);   // VEC: H % 8 == 0, so n = 4
   float pre[3][4], bh[4], hp[4], hnv[4], hv[4];
 #pragma unroll
@@ -542,6 +697,20 @@ __global__ void __launch_bounds__(NTHR) gru_fwd_kernel(const GruFwdArgs a) {
   }
 }
 
+template <bool VEC>
+__global__ void __launch_bounds__(NTHR) gru_fwd_kernel(const GruFwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * 3 * BSUB * WAVE];
+  gru_fwd_body<VEC>(a, red);
+}
+
+// both directions in one launch: blockIdx.z indexes the argument blocks
+template <bool VEC>
+__global__ void __launch_bounds__(NTHR)
+gru_fwd2_kernel(const Pair<GruFwdArgs> p) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * 3 * BSUB * WAVE];
+  gru_fwd_body<VEC>(p.d[blockIdx.z], red);
+}
+
 struct GruBwdArgs {
   const uint16_t* dgh_next; // [B][3H] bf16: dGh of step t + 1, or nullptr
   const uint16_t* WhT;      // [H][3H] bf16: Wh transposed
@@ -559,13 +728,12 @@ struct GruBwdArgs {
 };
 
 template <bool VEC>
-__global__ void __launch_bounds__(NTHR) gru_bwd_kernel(const GruBwdArgs a) {
-  __shared__ __attribute__((aligned(16))) float4 red[NW * BSUB * WAVE];
+__device__ __forceinline__ void gru_bwd_body(const GruBwdArgs& a, float4* red) {
   const int j0 = blockIdx.x * TH, b0 = blockIdx.y * TB;
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int B = a.B, H = a.H;
   f32x4 sum[1] = {f32x4{0, 0, 0, 0}};
-  if (a.dgh_next) {   // uniform over the grid
+  if (a.dgh_next) {   // uniform over the workgroup's direction
     f32x4 acc[1][BSUB];
 #pragma unroll
     for (int s = 0; s < BSUB; ++s) acc[0][s] = f32x4{0, 0, 0, 0};
@@ -608,26 +776,40 @@ __global__ void __launch_bounds__(NTHR) gru_bwd_kernel(const GruBwdArgs a) {
   st4h<VEC>(a.dgh + b * a.ld_dgh + 2ll * H + j, n, dnr);
 }
 
+template <bool VEC>
+__global__ void __launch_bounds__(NTHR) gru_bwd_kernel(const GruBwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * BSUB * WAVE];
+  gru_bwd_body<VEC>(a, red);
+}
+
+// both directions in one launch: blockIdx.z indexes the argument blocks
+template <bool VEC>
+__global__ void __launch_bounds__(NTHR)
+gru_bwd2_kernel(const Pair<GruBwdArgs> p) {
+  __shared__ __attribute__((aligned(16))) float4 red[NW * BSUB * WAVE];
+  gru_bwd_body<VEC>(p.d[blockIdx.z], red);
+}
+
 }  // namespace
 
 // One forward GRU time step (equations above).  h_prev nullptr: step 0, no
 // product, hn = b_hn.  hf_prev nullptr: zeros.  bhn nullptr: zeros.  gates
 // nullptr: not stored.  Every [B][.] operand has its own row pitch in
 // elements.
-HVK_API int hvk_gru_step_fwd(int B, int H, const void* h_prev,
-                             long long ld_hp, const void* Wh, long long ld_w,
-                             const float* xg, long long ld_xg,
-                             const float* hf_prev, long long ld_hfp,
-                             float* hf, long long ld_hf, float* hn,
-                             long long ld_hn, void* h, long long ld_h,
-                             void* gates, long long ld_g, const float* bhn,
-                             hipStream_t s) {
-  if (B < 1 || H < 1 || !xg || !h || !hf || !hn || (h_prev && !Wh)) return -1;
+namespace {
+
+bool gru_fwd_args(GruFwdArgs& a, bool& vec, int B, int H, const void* h_prev,
+                  long long ld_hp, const void* Wh, long long ld_w,
+                  const float* xg, long long ld_xg, const float* hf_prev,
+                  long long ld_hfp, float* hf, long long ld_hf, float* hn,
+                  long long ld_hn, void* h, long long ld_h, void* gates,
+                  long long ld_g, const float* bhn) {
+  if (B < 1 || H < 1 || !xg || !h || !hf || !hn || (h_prev && !Wh))
+    return false;
   if (ld_xg < 3ll * H || ld_h < H || ld_hf < H || ld_hn < H ||
       (h_prev && (ld_hp < H || ld_w < H)) || (hf_prev && ld_hfp < H) ||
       (gates && ld_g < 3ll * H))
-    return -1;
-  GruFwdArgs a;
+    return false;
   a.h_prev = (const uint16_t*)h_prev;
   a.Wh = (const uint16_t*)Wh;
   a.xg = xg;
@@ -640,18 +822,68 @@ HVK_API int hvk_gru_step_fwd(int B, int H, const void* h_prev,
   a.ld_hp = ld_hp; a.ld_w = ld_w; a.ld_xg = ld_xg; a.ld_hfp = ld_hfp;
   a.ld_hf = ld_hf; a.ld_hn = ld_hn; a.ld_h = ld_h; a.ld_g = ld_g;
   a.B = B; a.H = H;
-  const bool vec = H % 8 == 0 && on_grid(xg, ld_xg) && on_grid(h, ld_h) &&
-                   on_grid(hf, ld_hf) && on_grid(hn, ld_hn) &&
-                   (!h_prev || (on_grid(h_prev, ld_hp) && on_grid(Wh, ld_w))) &&
-                   (!hf_prev || on_grid(hf_prev, ld_hfp)) &&
-                   (!bhn || on_grid(bhn, 8)) &&
-                   (!gates || on_grid(gates, ld_g));
+  vec = H % 8 == 0 && on_grid(xg, ld_xg) && on_grid(h, ld_h) &&
+        on_grid(hf, ld_hf) && on_grid(hn, ld_hn) &&
+        (!h_prev || (on_grid(h_prev, ld_hp) && on_grid(Wh, ld_w))) &&
+        (!hf_prev || on_grid(hf_prev, ld_hfp)) &&
+        (!bhn || on_grid(bhn, 8)) && (!gates || on_grid(gates, ld_g));
+  return true;
+}
+
+}  // namespace
+
+HVK_API int hvk_gru_step_fwd(int B, int H, const void* h_prev,
+                             long long ld_hp, const void* Wh, long long ld_w,
+                             const float* xg, long long ld_xg,
+                             const float* hf_prev, long long ld_hfp,
+                             float* hf, long long ld_hf, float* hn,
+                             long long ld_hn, void* h, long long ld_h,
+                             void* gates, long long ld_g, const float* bhn,
+                             hipStream_t s) {
+  GruFwdArgs a;
+  bool vec;
+  if (!gru_fwd_args(a, vec, B, H, h_prev, ld_hp, Wh, ld_w, xg, ld_xg, hf_prev,
+                    ld_hfp, hf, ld_hf, hn, ld_hn, h, ld_h, gates, ld_g, bhn))
+    return -1;
   const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
   if (grid.y > 65535u) return -1;
   if (vec)
     hipLaunchKernelGGL((gru_fwd_kernel<true>), grid, dim3(NTHR), 0, s, a);
   else
     hipLaunchKernelGGL((gru_fwd_kernel<false>), grid, dim3(NTHR), 0, s, a);
+  return (int)launch_status(s);
+}
+
+// One forward GRU time step of both directions in one launch (grid.z = 2):
+// the operand list of hvk_gru_step_fwd once per direction, null operands per
+// direction, bit for bit what hvk_gru_step_fwd does on either.
+HVK_API int hvk_gru_step_fwd2(
+    int B, int H, const void* h_prev0, long long ld_hp0, const void* Wh0,
+    long long ld_w0, const float* xg0, long long ld_xg0,
+    const float* hf_prev0, long long ld_hfp0, float* hf0, long long ld_hf0,
+    float* hn0, long long ld_hn0, void* h0, long long ld_h0, void* gates0,
+    long long ld_g0, const float* bhn0, const void* h_prev1,
+    long long ld_hp1, const void* Wh1, long long ld_w1, const float* xg1,
+    long long ld_xg1, const float* hf_prev1, long long ld_hfp1, float* hf1,
+    long long ld_hf1, float* hn1, long long ld_hn1, void* h1, long long ld_h1,
+    void* gates1, long long ld_g1, const float* bhn1, hipStream_t s) {
+  Pair<GruFwdArgs> p;
+  GruFwdArgs &a0 = p.d[0], &a1 = p.d[1];
+  bool vec0, vec1;
+  if (!gru_fwd_args(a0, vec0, B, H, h_prev0, ld_hp0, Wh0, ld_w0, xg0, ld_xg0,
+                    hf_prev0, ld_hfp0, hf0, ld_hf0, hn0, ld_hn0, h0, ld_h0,
+                    gates0, ld_g0, bhn0) ||
+      !gru_fwd_args(a1, vec1, B, H, h_prev1, ld_hp1, Wh1, ld_w1, xg1, ld_xg1,
+                    hf_prev1, ld_hfp1, hf1, ld_hf1, hn1, ld_hn1, h1, ld_h1,
+                    gates1, ld_g1, bhn1))
+    return -1;
+  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB),
+                  2);
+  if (grid.y > 65535u) return -1;
+  if (vec0 && vec1)
+    hipLaunchKernelGGL((gru_fwd2_kernel<true>), grid, dim3(NTHR), 0, s, p);
+  else
+    hipLaunchKernelGGL((gru_fwd2_kernel<false>), grid, dim3(NTHR), 0, s, p);
   return (int)launch_status(s);
 }
 
@@ -662,25 +894,24 @@ HVK_API int hvk_gru_step_fwd(int B, int H, const void* h_prev,
 //   dr = dn hn r(1 - r)
 //   dgx = (dr, dz, dn),  dgh = (dr, dz, dn r),  dc_out = dh z
 // WhT is [H][3H], Wh transposed.  dc_out may alias dc_in.
-HVK_API int hvk_gru_step_bwd(int B, int H, const void* dgh_next,
-                             long long ld_dgn, const void* WhT,
-                             long long ld_wt, const void* err, long long ld_e,
-                             const void* gates, long long ld_g,
-                             const float* hn, long long ld_hn,
-                             const float* hf_prev, long long ld_hfp,
-                             const float* dc_in, long long ld_dci,
-                             float* dc_out, long long ld_dco, void* dgx,
-                             long long ld_dgx, void* dgh, long long ld_dgh,
-                             hipStream_t s) {
+namespace {
+
+bool gru_bwd_args(GruBwdArgs& a, bool& vec, int B, int H,
+                  const void* dgh_next, long long ld_dgn, const void* WhT,
+                  long long ld_wt, const void* err, long long ld_e,
+                  const void* gates, long long ld_g, const float* hn,
+                  long long ld_hn, const float* hf_prev, long long ld_hfp,
+                  const float* dc_in, long long ld_dci, float* dc_out,
+                  long long ld_dco, void* dgx, long long ld_dgx, void* dgh,
+                  long long ld_dgh) {
   if (B < 1 || H < 1 || !gates || !hn || !dc_out || !dgx || !dgh ||
       (dgh_next && !WhT))
-    return -1;
+    return false;
   const long long gh = 3ll * H;
   if (ld_dgx < gh || ld_dgh < gh || ld_g < gh || ld_hn < H || ld_dco < H ||
       (dgh_next && (ld_dgn < gh || ld_wt < gh)) || (err && ld_e < H) ||
       (hf_prev && ld_hfp < H) || (dc_in && ld_dci < H))
-    return -1;
-  GruBwdArgs a;
+    return false;
   a.dgh_next = (const uint16_t*)dgh_next;
   a.WhT = (const uint16_t*)WhT;
   a.err = (const uint16_t*)err;
@@ -695,19 +926,77 @@ HVK_API int hvk_gru_step_bwd(int B, int H, const void* dgh_next,
   a.ld_hn = ld_hn; a.ld_hfp = ld_hfp; a.ld_dci = ld_dci; a.ld_dco = ld_dco;
   a.ld_dgx = ld_dgx; a.ld_dgh = ld_dgh;
   a.B = B; a.H = H;
-  const bool vec = H % 8 == 0 && on_grid(dgx, ld_dgx) && on_grid(dgh, ld_dgh) &&
-                   on_grid(gates, ld_g) && on_grid(hn, ld_hn) &&
-                   on_grid(dc_out, ld_dco) &&
-                   (!dgh_next ||
-                    (on_grid(dgh_next, ld_dgn) && on_grid(WhT, ld_wt))) &&
-                   (!err || on_grid(err, ld_e)) &&
-                   (!hf_prev || on_grid(hf_prev, ld_hfp)) &&
-                   (!dc_in || on_grid(dc_in, ld_dci));
+  vec = H % 8 == 0 && on_grid(dgx, ld_dgx) && on_grid(dgh, ld_dgh) &&
+        on_grid(gates, ld_g) && on_grid(hn, ld_hn) &&
+        on_grid(dc_out, ld_dco) &&
+        (!dgh_next || (on_grid(dgh_next, ld_dgn) && on_grid(WhT, ld_wt))) &&
+        (!err || on_grid(err, ld_e)) &&
+        (!hf_prev || on_grid(hf_prev, ld_hfp)) &&
+        (!dc_in || on_grid(dc_in, ld_dci));
+  return true;
+}
+
+}  // namespace
+
+HVK_API int hvk_gru_step_bwd(int B, int H, const void* dgh_next,
+                             long long ld_dgn, const void* WhT,
+                             long long ld_wt, const void* err, long long ld_e,
+                             const void* gates, long long ld_g,
+                             const float* hn, long long ld_hn,
+                             const float* hf_prev, long long ld_hfp,
+                             const float* dc_in, long long ld_dci,
+                             float* dc_out, long long ld_dco, void* dgx,
+                             long long ld_dgx, void* dgh, long long ld_dgh,
+                             hipStream_t s) {
+  GruBwdArgs a;
+  bool vec;
+  if (!gru_bwd_args(a, vec, B, H, dgh_next, ld_dgn, WhT, ld_wt, err, ld_e,
+                    gates, ld_g, hn, ld_hn, hf_prev, ld_hfp, dc_in, ld_dci,
+                    dc_out, ld_dco, dgx, ld_dgx, dgh, ld_dgh))
+    return -1;
   const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
   if (grid.y > 65535u) return -1;
   if (vec)
     hipLaunchKernelGGL((gru_bwd_kernel<true>), grid, dim3(NTHR), 0, s, a);
   else
     hipLaunchKernelGGL((gru_bwd_kernel<false>), grid, dim3(NTHR), 0, s, a);
+  return (int)launch_status(s);
+}
+
+// One backward GRU time step of both directions in one launch (grid.z = 2):
+// the operand list of hvk_gru_step_bwd once per direction, null operands per
+// direction, bit for bit what hvk_gru_step_bwd does on either.
+HVK_API int hvk_gru_step_bwd2(
+    int B, int H, const void* dgh_next0, long long ld_dgn0, const void* WhT0,
+    long long ld_wt0, const void* err0, long long ld_e0, const void* gates0,
+    long long ld_g0, const float* hn0, long long ld_hn0,
+    const float* hf_prev0, long long ld_hfp0, const float* dc_in0,
+    long long ld_dci0, float* dc_out0, long long ld_dco0, void* dgx0,
+    long long ld_dgx0, void* dgh0, long long ld_dgh0, const void* dgh_next1,
+    long long ld_dgn1, const void* WhT1, long long ld_wt1, const void* err1,
+    long long ld_e1, const void* gates1, long long ld_g1, const float* hn1,
+    long long ld_hn1, const float* hf_prev1, long long ld_hfp1,
+    const float* dc_in1, long long ld_dci1, float* dc_out1,
+    long long ld_dco1, void* dgx1, long long ld_dgx1, void* dgh1,
+    long long ld_dgh1, hipStream_t s) {
+  Pair<GruBwdArgs> p;
+  GruBwdArgs &a0 = p.d[0], &a1 = p.d[1];
+  bool vec0, vec1;
+  if (!gru_bwd_args(a0, vec0, B, H, dgh_next0, ld_dgn0, WhT0, ld_wt0, err0,
+                    ld_e0, gates0, ld_g0, hn0, ld_hn0, hf_prev0, ld_hfp0,
+                    dc_in0, ld_dci0, dc_out0, ld_dco0, dgx0, ld_dgx0, dgh0,
+                    ld_dgh0) ||
+      !gru_bwd_args(a1, vec1, B, H, dgh_next1, ld_dgn1, WhT1, ld_wt1, err1,
+                    ld_e1, gates1, ld_g1, hn1, ld_hn1, hf_prev1, ld_hfp1,
+                    dc_in1, ld_dci1, dc_out1, ld_dco1, dgx1, ld_dgx1, dgh1,
+                    ld_dgh1))
+    return -1;
+  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB),
+                  2);
+  if (grid.y > 65535u) return -1;
+  if (vec0 && vec1)
+    hipLaunchKernelGGL((gru_bwd2_kernel<true>), grid, dim3(NTHR), 0, s, p);
+  else
+    hipLaunchKernelGGL((gru_bwd2_kernel<false>), grid, dim3(NTHR), 0, s, p);
   return (int)launch_status(s);
 }

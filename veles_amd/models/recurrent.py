@@ -23,6 +23,13 @@ GRU (pinned to torch.nn.GRU, parity unpinned): gate order r, z, n,
 
 ``weights`` [3H][I+H], ``bias`` [4H] = (b_r, b_z, b_n, b_hn), all filled
 uniformly with fan-in I + H; no forget bias (``ops.gru_fwd`` / ``gru_bwd``).
+
+``bidirectional`` (D = 2 directions) adds a reverse chain h^r_t =
+cell(x_t, h^r_{t+1}) with parameters of its own: ``weights``
+[D*NG*H][I+H] and ``bias`` are direction-major, each block the one-direction
+layout; the output is (T, 2H) = [h^f_t | h^r_t] or (2H,) =
+[h^f_{T-1} | h^r_0] (torch's ``output`` / ``h_n``).  ``reverse`` runs the
+reverse chain alone (docs/OPS.md "Bidirectional").
 """
 from __future__ import annotations
 
@@ -54,6 +61,11 @@ class LSTM(Forward):
         self.hidden = int(oss)
         self.return_sequences = bool(kwargs.get("return_sequences", False))
         self.forget_bias = float(kwargs.get("forget_bias", 1.0))
+        self.bidirectional = bool(kwargs.get("bidirectional", False))
+        self.reverse = bool(kwargs.get("reverse", False))
+        if self.bidirectional and self.reverse:
+            raise ValueError("%s: bidirectional and reverse exclude each "
+                             "other" % self.name)
         if self.weights_transposed:
             raise ValueError("%s: weights_transposed is not supported" %
                              self.name)
@@ -63,13 +75,25 @@ class LSTM(Forward):
         self.save_ = {}
 
     @property
+    def direction(self):
+        """the ops' ``direction``; a layer pickled before the attributes
+        existed runs forward-only"""
+        if getattr(self, "bidirectional", False):
+            return "both"
+        return "reverse" if getattr(self, "reverse", False) else "forward"
+
+    @property
+    def directions(self):
+        return 2 if self.direction == "both" else 1
+
+    @property
     def neurons_number(self):
-        return self.hidden
+        return self.directions * self.hidden
 
     @property
     def output_sample_shape(self):
-        return (self.steps, self.hidden) if self.return_sequences else \
-            (self.hidden,)
+        width = self.directions * self.hidden
+        return (self.steps, width) if self.return_sequences else (width,)
 
     def initialize(self, device=None, **kwargs):
         super().initialize(device=device, **kwargs)
@@ -78,9 +102,9 @@ class LSTM(Forward):
             raise ValueError("%s: input samples must be (T, I), got %s" %
                              (self.name, shape[1:]))
         B, self.steps, n_in = shape
-        H, ng = self.hidden, self.GATES
+        H, ng, D = self.hidden, self.GATES, self.directions
         fan_in = n_in + H
-        wshape = (ng * H, fan_in)
+        wshape = (D * ng * H, fan_in)
         # created here, weights before bias as register_params would, so that
         # the forget gate's bias can start at forget_bias
         std = 1.0 / numpy.sqrt(fan_in)
@@ -90,7 +114,7 @@ class LSTM(Forward):
                          std if self.weights_stddev is None
                          else self.weights_stddev, self.rand)
             self.weights.reset(w)
-        nb = self.BIAS_BLOCKS * H
+        nb = D * self.BIAS_BLOCKS * H
         if self.include_bias and (self.bias.mem is None or
                                   self.bias.mem.shape != (nb,)):
             b = numpy.zeros(nb, numpy.float32)
@@ -98,7 +122,8 @@ class LSTM(Forward):
                          std if self.bias_stddev is None
                          else self.bias_stddev, self.rand)
             if ng == 4:
-                b[H:2 * H] = self.forget_bias
+                for d in range(D):
+                    b[(4 * d + 1) * H:(4 * d + 2) * H] = self.forget_bias
             self.bias.reset(b)
         self.register_params(wshape, fan_in, bias_len=nb)
         self.save_ = {}
@@ -114,7 +139,8 @@ class LSTM(Forward):
         B = x.shape[0]
         seq = self.return_sequences
         testing = bool(getattr(self.workflow, "testing", False))
-        out = None if seq else self.alloc_output((B, self.hidden))
+        out = None if seq else self.alloc_output(
+            (B, self.directions * self.hidden))
         y = self.forward_op(x, w, return_sequences=seq,
                             save=None if testing else self.save_,
                             ws=self.save_, out=out)
@@ -123,7 +149,8 @@ class LSTM(Forward):
 
     def forward_op(self, x, w, **kwargs):
         return ops.lstm_fwd(x, w, self.bias_master, self.hidden,
-                            cell=self.CELL, **kwargs)
+                            cell=self.CELL, direction=self.direction,
+                            **kwargs)
 
 
 class RNN(LSTM):
@@ -142,7 +169,8 @@ class GRU(LSTM):
     BIAS_BLOCKS = 4   # (b_r, b_z, b_n, b_hn)
 
     def forward_op(self, x, w, **kwargs):
-        return ops.gru_fwd(x, w, self.bias_master, self.hidden, **kwargs)
+        return ops.gru_fwd(x, w, self.bias_master, self.hidden,
+                           direction=self.direction, **kwargs)
 
 
 class GDLSTM(GradientDescentBase):
@@ -167,8 +195,9 @@ class GDLSTM(GradientDescentBase):
         err = self.err_output.devmem
         if err.dtype != w.dtype:
             err = err.to(w.dtype)
-        err = err.reshape((B, T, fwd.hidden) if fwd.return_sequences
-                          else (B, fwd.hidden))
+        width = fwd.directions * fwd.hidden
+        err = err.reshape((B, T, width) if fwd.return_sequences
+                          else (B, width))
         pw, pb = fwd._pw_, fwd._pb_
         # the step's only contribution: write, not read-modify-write
         mode = "overwrite" if self.store_.overwrite else True
@@ -181,7 +210,7 @@ class GDLSTM(GradientDescentBase):
     def backward_op(self, err, x, w, fwd, dw, dbias, mode, ei):
         ops.lstm_bwd(err, x, w, fwd.save_, dw, dbias, cell=fwd.CELL,
                      accumulate=mode, need_err_input=self.need_err_input,
-                     err_input=ei)
+                     err_input=ei, direction=fwd.direction)
 
 
 class GDRNN(GDLSTM):
@@ -193,4 +222,5 @@ class GDGRU(GDLSTM):
 
     def backward_op(self, err, x, w, fwd, dw, dbias, mode, ei):
         ops.gru_bwd(err, x, w, fwd.save_, dw, dbias, accumulate=mode,
-                    need_err_input=self.need_err_input, err_input=ei)
+                    need_err_input=self.need_err_input, err_input=ei,
+                    direction=fwd.direction)

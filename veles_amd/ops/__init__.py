@@ -2562,9 +2562,9 @@ def _rec_buf(store, key, shape, dtype, dev, zero=False):
     return t
 
 
-def _lstm_args(name, x, w, bias, H, cell):
-    """Shared host checks of lstm_fwd / lstm_bwd; returns (B, T, I, H, kernel
-    cell code, gates)."""
+def _lstm_args(name, x, w, bias, H, cell, D=1):
+    """Shared host checks of lstm_fwd / lstm_bwd over ``D`` directions;
+    returns (B, T, I, H, kernel cell code, gates)."""
     if cell not in _CELLS:
         raise ValueError("%s: unknown cell %r (lstm, rnn)" % (name, cell))
     code, ng = _CELLS[cell]
@@ -2573,9 +2573,9 @@ def _lstm_args(name, x, w, bias, H, cell):
         raise ValueError("%s: input must be [B][T][I], got %s" %
                          (name, tuple(x.shape)))
     B, T, I = x.shape
-    if H < 1 or w.dim() != 2 or tuple(w.shape) != (ng * H, I + H):
+    if H < 1 or w.dim() != 2 or tuple(w.shape) != (D * ng * H, I + H):
         raise ValueError("%s: weights must be [%d][%d] (%s, I = %d, H = %d), "
-                         "got %s" % (name, ng * H, I + H, cell, I, H,
+                         "got %s" % (name, D * ng * H, I + H, cell, I, H,
                                      tuple(w.shape)))
     if x.device != w.device or (bias is not None and bias.device != w.device):
         raise ValueError("%s: operands on different devices" % name)
@@ -2583,10 +2583,10 @@ def _lstm_args(name, x, w, bias, H, cell):
         raise ValueError("%s: input rows must be contiguous with one pitch "
                          "over [B][T], weight rows contiguous (strides %s, "
                          "%s)" % (name, x.stride(), w.stride()))
-    if bias is not None and (tuple(bias.shape) != (ng * H,) or
+    if bias is not None and (tuple(bias.shape) != (D * ng * H,) or
                              not bias.is_contiguous()):
         raise ValueError("%s: bias must be a contiguous [%d], got %s" %
-                         (name, ng * H, tuple(bias.shape)))
+                         (name, D * ng * H, tuple(bias.shape)))
     if _gpu(w):
         if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
             raise TypeError("%s: GPU input and weights must be bfloat16, got "
@@ -2599,9 +2599,9 @@ def _lstm_args(name, x, w, bias, H, cell):
     elif not (x.is_floating_point() and w.is_floating_point()):
         raise TypeError("%s: floating-point operands, got %s / %s" %
                         (name, x.dtype, w.dtype))
-    if B * T * max(_r8(ng * H), x.stride(1)) >= 1 << 31:
+    if B * T * max(_r8(D * ng * H), x.stride(1)) >= 1 << 31:
         raise ValueError("%s: %d x %d x %d exceeds 2^31 elements" %
-                         (name, B, T, max(ng * H, I)))
+                         (name, B, T, max(D * ng * H, I)))
     return B, T, I, H, code, ng
 
 
@@ -2611,7 +2611,7 @@ def _rows(x, B, T):
 
 
 def lstm_fwd(x, w, bias, H, *, cell="lstm", return_sequences=False,
-             save=None, out=None, ws=None):
+             save=None, out=None, ws=None, direction="forward"):
     """Forward of a recurrent layer over ``x`` [B][T][I] (batch-major).
 
     ``w`` [NG*H][I+H] is ONE parameter: ``w[:, :I]`` is Wx, ``w[:, I:]`` is
@@ -2628,8 +2628,13 @@ def lstm_fwd(x, w, bias, H, *, cell="lstm", return_sequences=False,
     ``save`` (a dict) receives "h" [B][T][H], "c" [B][T][H] float32, "gates"
     [B][T][NG*H] (post-activation; lstm only) and "xg" for lstm_bwd; with
     ``save=None`` the gates are not written.  A kept ``save`` / ``ws`` dict
-    is reused: no allocation from the second call on."""
+    is reused: no allocation from the second call on.
+
+    ``direction="reverse"`` / ``"both"``: see ``_lstm_fwd_dir``."""
     name = "lstm_fwd"
+    if direction != "forward":
+        return _lstm_fwd_dir(x, w, bias, H, cell, return_sequences, save,
+                             out, ws, direction)
     B, T, I, H, code, ng = _lstm_args(name, x, w, bias, H, cell)
     dev = x.device
     st = save if save is not None else (ws if ws is not None else {})
@@ -2706,7 +2711,7 @@ def lstm_fwd(x, w, bias, H, *, cell="lstm", return_sequences=False,
 
 
 def lstm_bwd(err, x, w, save, dw, dbias, *, cell="lstm", accumulate="overwrite",
-             need_err_input=True, err_input=None):
+             need_err_input=True, err_input=None, direction="forward"):
     """Backward of lstm_fwd from its ``save`` dict.
 
     ``err`` is dL/dh_T [B][H], or dL/dh_t for every step [B][T][H] (the
@@ -2716,8 +2721,13 @@ def lstm_bwd(err, x, w, save, dw, dbias, *, cell="lstm", accumulate="overwrite",
     ``dw[:, I:]`` (+)= dG^T.H_prev over all B*T rows (``accumulate``: True
     adds, "overwrite" writes, as in ``gemm``), and, with ``need_err_input``,
     err_input [B][T][I] = dG.Wx is returned.  ``dw`` is float32 [NG*H][I+H], ``dbias`` float32 [NG*H] or
-    None.  Bit-reproducible under ``set_deterministic(True)``."""
+    None.  Bit-reproducible under ``set_deterministic(True)``.
+
+    ``direction="reverse"`` / ``"both"``: see ``_lstm_bwd_dir``."""
     name = "lstm_bwd"
+    if direction != "forward":
+        return _lstm_bwd_dir(err, x, w, save, dw, dbias, cell, accumulate,
+                             need_err_input, err_input, direction)
     if cell not in _CELLS:
         raise ValueError("%s: unknown cell %r (lstm, rnn)" % (name, cell))
     ng = _CELLS[cell][1]
@@ -2847,16 +2857,17 @@ def lstm_bwd(err, x, w, save, dw, dbias, *, cell="lstm", accumulate="overwrite",
 
 # GRU (docs/OPS.md "GRU"): gate order r, z, n; the reset gate multiplies the
 # hidden-side product only, so it has step kernels and entry points of its own.
-def _gru_args(name, x, w, bias, H):
-    """Shared host checks of gru_fwd / gru_bwd; returns (B, T, I, H)."""
+def _gru_args(name, x, w, bias, H, D=1):
+    """Shared host checks of gru_fwd / gru_bwd over ``D`` directions; returns
+    (B, T, I, H)."""
     H = int(H)
     if x.dim() != 3 or min(x.shape) < 1:
         raise ValueError("%s: input must be [B][T][I], got %s" %
                          (name, tuple(x.shape)))
     B, T, I = x.shape
-    if H < 1 or w.dim() != 2 or tuple(w.shape) != (3 * H, I + H):
+    if H < 1 or w.dim() != 2 or tuple(w.shape) != (D * 3 * H, I + H):
         raise ValueError("%s: weights must be [%d][%d] (I = %d, H = %d), "
-                         "got %s" % (name, 3 * H, I + H, I, H,
+                         "got %s" % (name, D * 3 * H, I + H, I, H,
                                      tuple(w.shape)))
     if x.device != w.device or (bias is not None and bias.device != w.device):
         raise ValueError("%s: operands on different devices" % name)
@@ -2864,11 +2875,11 @@ def _gru_args(name, x, w, bias, H):
         raise ValueError("%s: input rows must be contiguous with one pitch "
                          "over [B][T], weight rows contiguous (strides %s, "
                          "%s)" % (name, x.stride(), w.stride()))
-    if bias is not None and (tuple(bias.shape) != (4 * H,) or
+    if bias is not None and (tuple(bias.shape) != (D * 4 * H,) or
                              not bias.is_contiguous()):
         raise ValueError("%s: bias must be a contiguous [%d] = (b_r, b_z, "
-                         "b_n, b_hn), got %s" %
-                         (name, 4 * H, tuple(bias.shape)))
+                         "b_n, b_hn) per direction, got %s" %
+                         (name, D * 4 * H, tuple(bias.shape)))
     if _gpu(w):
         if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
             raise TypeError("%s: GPU input and weights must be bfloat16, got "
@@ -2881,14 +2892,14 @@ def _gru_args(name, x, w, bias, H):
     elif not (x.is_floating_point() and w.is_floating_point()):
         raise TypeError("%s: floating-point operands, got %s / %s" %
                         (name, x.dtype, w.dtype))
-    if B * T * max(_r8(3 * H), x.stride(1)) >= 1 << 31:
+    if B * T * max(_r8(D * 3 * H), x.stride(1)) >= 1 << 31:
         raise ValueError("%s: %d x %d x %d exceeds 2^31 elements" %
-                         (name, B, T, max(3 * H, I)))
+                         (name, B, T, max(D * 3 * H, I)))
     return B, T, I, H
 
 
 def gru_fwd(x, w, bias, H, *, return_sequences=False, save=None, out=None,
-            ws=None):
+            ws=None, direction="forward"):
     """Forward of a GRU layer over ``x`` [B][T][I] (batch-major).
 
     ``w`` [3H][I+H] is ONE parameter: ``w[:, :I]`` is Wx, ``w[:, I:]`` is Wh,
@@ -2907,8 +2918,13 @@ def gru_fwd(x, w, bias, H, *, return_sequences=False, save=None, out=None,
     in float32: the carry z h_{t-1} is not rounded to bf16), "hn" float32,
     "gates" [B][T][3H] (post-activation r, z, n) and "xg" for gru_bwd; with
     ``save=None`` the gates are not written.  A kept ``save`` / ``ws`` dict
-    is reused: no allocation from the second call on."""
+    is reused: no allocation from the second call on.
+
+    ``direction="reverse"`` / ``"both"``: see ``_gru_fwd_dir``."""
     name = "gru_fwd"
+    if direction != "forward":
+        return _gru_fwd_dir(x, w, bias, H, return_sequences, save, out, ws,
+                            direction)
     B, T, I, H = _gru_args(name, x, w, bias, H)
     dev = x.device
     st = save if save is not None else (ws if ws is not None else {})
@@ -2983,7 +2999,7 @@ def gru_fwd(x, w, bias, H, *, return_sequences=False, save=None, out=None,
 
 
 def gru_bwd(err, x, w, save, dw, dbias, *, accumulate="overwrite",
-            need_err_input=True, err_input=None):
+            need_err_input=True, err_input=None, direction="forward"):
     """Backward of gru_fwd from its ``save`` dict.
 
     ``err`` is dL/dh_T [B][H], or dL/dh_t for every step [B][T][H] (the
@@ -3002,8 +3018,13 @@ def gru_bwd(err, x, w, save, dw, dbias, *, accumulate="overwrite",
     adds, "overwrite" writes, as in ``gemm``), and, with ``need_err_input``,
     err_input [B][T][I] = dGx.Wx is returned.  ``dw`` is float32 [3H][I+H],
     ``dbias`` float32 [4H] or None.  Bit-reproducible under
-    ``set_deterministic(True)``."""
+    ``set_deterministic(True)``.
+
+    ``direction="reverse"`` / ``"both"``: see ``_gru_bwd_dir``."""
     name = "gru_bwd"
+    if direction != "forward":
+        return _gru_bwd_dir(err, x, w, save, dw, dbias, accumulate,
+                            need_err_input, err_input, direction)
     if w.dim() != 2 or w.shape[0] % 3:
         raise ValueError("%s: weights %s" % (name, tuple(w.shape)))
     B, T, I, H = _gru_args(name, x, w, None, w.shape[0] // 3)
@@ -3128,6 +3149,578 @@ def gru_bwd(err, x, w, save, dw, dbias, *, accumulate="overwrite",
             dbias[gh:] += sums[2 * H:]
         else:
             dbias[gh:].copy_(sums[2 * H:])
+    if not need_err_input:
+        return None
+    if err_input is None:
+        err_input = torch.empty(B, T, I, dtype=hdt, device=dev)
+    gemm(dgx2, w[:, :I], out=err_input.view(B * T, I))
+    return err_input
+
+
+# Reverse and bidirectional layers (docs/OPS.md "Bidirectional").  A direction
+# is (d, rev): its block index along every direction-major axis and whether
+# its chain runs t = T-1 .. 0.  Every wide buffer is [B][T][D*W] with
+# direction d at [..., d*W:(d+1)*W] (W = H or NG*H; the pitch of the private
+# padded ones is D*W rounded up to 8), so the kernels write both halves of
+# the [B][T][2H] output through their row pitches: no flip, no concat.
+_DIRS = {"reverse": ((0, True),), "both": ((0, False), (1, True))}
+
+# "both": one paired launch per step (True) or the chain of 2T one-direction
+# launches over the same buffers (False; the A/B of tools/bench_birecurrent)
+_BI_PAIRED = True
+
+
+def set_birecurrent_paired(on):
+    """``direction="both"`` through the paired step launches (default) or
+    through one-direction launches, two per step; returns the old value."""
+    global _BI_PAIRED
+    old, _BI_PAIRED = _BI_PAIRED, bool(on)
+    return old
+
+
+def _directions(name, direction):
+    if direction not in _DIRS:
+        raise ValueError("%s: unknown direction %r (forward, reverse, both)" %
+                         (name, direction))
+    return _DIRS[direction]
+
+
+def _bi_steps(fn1, fn2, name, head, dirs, T, step, stream):
+    """The T step launches of one pass: ``step(d, rev, s)`` is the operand
+    list of direction (d, rev) at launch ``s`` of its chain."""
+    for s in range(T):
+        if len(dirs) == 2 and _BI_PAIRED:
+            rc = fn2(*(head + step(0, False, s) + step(1, True, s) +
+                       (stream,)))
+            if rc:
+                _lib.check(rc, name + "2")
+            continue
+        for d, rev in dirs:
+            rc = fn1(*(head + step(d, rev, s) + (stream,)))
+            if rc:
+                _lib.check(rc, name)
+
+
+def _bi_last(h_all, dirs, H, T, out):
+    """[h^f_{T-1} | h^r_0]: the final state of every direction"""
+    if out is None:
+        out = torch.empty(h_all.shape[0], len(dirs) * H, dtype=h_all.dtype,
+                          device=h_all.device)
+    for d, rev in dirs:
+        out[:, d * H:(d + 1) * H].copy_(
+            h_all[:, 0 if rev else T - 1, d * H:(d + 1) * H])
+    return out
+
+
+def _bi_hprev(save, h_all, dirs, B, T, H):
+    """The chain's previous h of every row: h shifted by one step towards the
+    chain's end, zeros at its first step (the buffer is zeroed once and those
+    rows are never written)."""
+    hp = _rec_buf(save, "_hprev", tuple(h_all.shape), h_all.dtype,
+                  h_all.device, zero=True)
+    if T > 1:
+        for d, rev in dirs:
+            sl = slice(d * H, (d + 1) * H)
+            if rev:
+                hp[:, :T - 1, sl].copy_(h_all[:, 1:, sl])
+            else:
+                hp[:, 1:, sl].copy_(h_all[:, :T - 1, sl])
+    return hp
+
+
+def _bi_err_check(name, err, B, T, DH, dev):
+    seq = err.dim() == 3
+    if tuple(err.shape) != ((B, T, DH) if seq else (B, DH)) or \
+            err.stride(-1) != 1 or err.device != dev:
+        raise ValueError("%s: err must be [%d][%d] or [%d][%d][%d] with "
+                         "contiguous rows on %s, got %s" %
+                         (name, B, DH, B, T, DH, dev, tuple(err.shape)))
+    return seq
+
+
+def _lstm_fwd_dir(x, w, bias, H, cell, return_sequences, save, out, ws,
+                  direction):
+    """lstm_fwd for ``direction="reverse"`` (D = 1: the same cell from
+    t = T-1 down to 0, h^r_t = cell(x_t, h^r_{t+1}), output aligned with the
+    input's time axis or h^r_0) and ``"both"`` (D = 2).
+
+    ``w`` [D*NG*H][I+H] and ``bias`` [D*NG*H] are direction-major, each block
+    the one-direction layout.  Returns [B][T][D*H] = [h^f_t | h^r_t] with
+    ``return_sequences``, else [B][D*H] = [h^f_{T-1} | h^r_0].  ``save`` keeps
+    the keys of lstm_fwd, every feature axis D times as wide, direction d at
+    ``[..., d*W:(d+1)*W]``.  "both" on the GPU: one projection GEMM over both
+    directions, then T paired launches on the current stream (forward chain
+    at t = s, reverse chain at t = T-1-s)."""
+    name = "lstm_fwd"
+    dirs = _directions(name, direction)
+    D = len(dirs)
+    B, T, I, H, code, ng = _lstm_args(name, x, w, bias, H, cell, D)
+    dev = x.device
+    st = save if save is not None else (ws if ws is not None else {})
+    gh = ng * H
+    W = D * gh
+    lstm = ng == 4
+    if out is not None and not return_sequences and (
+            tuple(out.shape) != (B, D * H) or out.device != dev):
+        raise ValueError("%s: out must be [%d][%d] on %s" %
+                         (name, B, D * H, dev))
+    if _gpu(x):
+        fn1 = _rec_fn("hvk_lstm_step_fwd")
+        fn2 = _rec_fn("hvk_lstm_step_fwd2") if D == 2 else None
+        PW = _r8(W)
+        xg_ = _rec_buf(st, "_xg", (B, T, PW), torch.float32, dev)
+        h_all = _rec_buf(st, "h", (B, T, D * H), torch.bfloat16, dev)
+        c_all = _rec_buf(st, "c", (B, T, D * H), torch.float32, dev) \
+            if lstm else None
+        g_ = _rec_buf(st, "_gates", (B, T, PW), torch.bfloat16, dev) \
+            if lstm and save is not None else None
+        gemm(_rows(x, B, T), w[:, :I], trans_b=True, bias=bias,
+             out=xg_.view(B * T, PW)[:, :W])
+        ph, pc, pxg = h_all.data_ptr(), _p(c_all), xg_.data_ptr()
+        pg = _p(g_)
+        pw, ldw = w.data_ptr() + 2 * I, w.stride(0)
+        DH, ldh, ldp = D * H, T * D * H, T * PW
+
+        def step(d, rev, s):
+            t = T - 1 - s if rev else s
+            tp = t + 1 if rev else t - 1
+            oh, og = d * H, d * gh
+            return (ph + 2 * (tp * DH + oh) if s else None, ldh,
+                    pw + 2 * og * ldw, ldw,
+                    pxg + 4 * (t * PW + og), ldp,
+                    pc + 4 * (tp * DH + oh) if lstm and s else None, ldh,
+                    pc + 4 * (t * DH + oh) if lstm else None, ldh,
+                    ph + 2 * (t * DH + oh), ldh,
+                    pg + 2 * (t * PW + og) if pg else None, ldp)
+        _bi_steps(fn1, fn2, "hvk_lstm_step_fwd", (code, B, H), dirs, T, step,
+                  _s(x))
+        if save is not None:
+            save["xg"] = xg_[:, :, :W]
+            if lstm:
+                save["gates"] = g_[:, :, :W]
+    else:
+        xf, wf = x.float(), w.float()
+        xg = xf.reshape(B * T, I) @ wf[:, :I].t()
+        if bias is not None:
+            xg = xg + bias.float().view(1, -1)
+        xg = xg.view(B, T, W)
+        h_all = _rec_buf(st, "h", (B, T, D * H), torch.float32, dev)
+        if lstm:
+            c_all = _rec_buf(st, "c", (B, T, D * H), torch.float32, dev)
+            gates = _rec_buf(st, "gates", (B, T, W), torch.float32, dev)
+        for d, rev in dirs:
+            wh = wf[d * gh:(d + 1) * gh, I:]
+            h = torch.zeros(B, H)
+            c = torch.zeros(B, H)
+            for s in range(T):
+                t = T - 1 - s if rev else s
+                pre = xg[:, t, d * gh:(d + 1) * gh]
+                if s:
+                    pre = pre + h @ wh.t()
+                if lstm:
+                    gi = torch.sigmoid(pre[:, :H])
+                    gf = torch.sigmoid(pre[:, H:2 * H])
+                    gg = torch.tanh(pre[:, 2 * H:3 * H])
+                    go = torch.sigmoid(pre[:, 3 * H:])
+                    c = gf * c + gi * gg
+                    h = go * torch.tanh(c)
+                    c_all[:, t, d * H:(d + 1) * H] = c
+                    gates[:, t, d * gh:(d + 1) * gh] = \
+                        torch.cat((gi, gf, gg, go), 1)
+                else:
+                    h = torch.tanh(pre)
+                h_all[:, t, d * H:(d + 1) * H] = h
+        if save is not None:
+            save["xg"] = xg
+    if return_sequences:
+        return h_all
+    return _bi_last(h_all, dirs, H, T, out)
+
+
+def _lstm_bwd_dir(err, x, w, save, dw, dbias, cell, accumulate,
+                  need_err_input, err_input, direction):
+    """lstm_bwd for ``direction="reverse"`` / ``"both"``.
+
+    ``err`` is [B][T][D*H], or [B][D*H] = the error of [h^f_{T-1} | h^r_0]:
+    its first half enters the forward chain at t = T-1, its second half the
+    reverse chain at t = 0.  The backward walks every chain from its end
+    ("both": one paired launch per step, forward chain at t = T-1-s, reverse
+    chain at t = s).  The weight rows of direction d take dG_d^T.X and
+    dG_d^T.Hprev_d (Hprev_f[t] = h^f_{t-1}, Hprev_r[t] = h^r_{t+1}, zero at
+    the chain's first step); ``dbias`` is direction-major; err_input =
+    sum_d dG_d.Wx_d is ONE GEMM over K = D*NG*H (no atomic accumulation)."""
+    name = "lstm_bwd"
+    dirs = _directions(name, direction)
+    D = len(dirs)
+    if cell not in _CELLS:
+        raise ValueError("%s: unknown cell %r (lstm, rnn)" % (name, cell))
+    ng = _CELLS[cell][1]
+    if w.dim() != 2 or w.shape[0] % (D * ng):
+        raise ValueError("%s: weights %s" % (name, tuple(w.shape)))
+    B, T, I, H, code, ng = _lstm_args(name, x, w, None,
+                                      w.shape[0] // (D * ng), cell, D)
+    dev = x.device
+    gh = ng * H
+    W = D * gh
+    DH = D * H
+    lstm = ng == 4
+    if accumulate not in (True, "overwrite"):
+        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
+                         name)
+    seq = _bi_err_check(name, err, B, T, DH, dev)
+    if dw.dtype != torch.float32 or tuple(dw.shape) != (W, I + H) or \
+            dw.stride(1) != 1 or dw.device != dev:
+        raise ValueError("%s: dw must be float32 [%d][%d] on %s" %
+                         (name, W, I + H, dev))
+    if dbias is not None and (dbias.dtype != torch.float32 or
+                              tuple(dbias.shape) != (W,) or
+                              not dbias.is_contiguous() or
+                              dbias.device != dev):
+        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
+                         % (name, W, dev))
+    hdt = torch.bfloat16 if _gpu(x) else torch.float32
+    need = [("h", (B, T, DH), hdt)]
+    if lstm:
+        need += [("c", (B, T, DH), torch.float32), ("gates", (B, T, W), hdt)]
+    for k, shape, dt in need:
+        t = None if save is None else save.get(k)
+        if t is None or tuple(t.shape) != shape or t.dtype != dt or \
+                t.device != dev:
+            raise ValueError("%s: save[%r] must be %s %s from lstm_fwd" %
+                             (name, k, dt, shape))
+    if need_err_input and err_input is not None and (
+            tuple(err_input.shape) != (B, T, I) or
+            not err_input.is_contiguous() or err_input.device != dev or
+            err_input.dtype != hdt):
+        raise ValueError("%s: err_input must be a contiguous %s [%d][%d][%d]"
+                         % (name, hdt, B, T, I))
+    h_all = save["h"]
+    if _gpu(x):
+        if err.dtype != torch.bfloat16:
+            raise TypeError("%s: GPU err must be bfloat16, got %s" %
+                            (name, err.dtype))
+        fn1 = _rec_fn("hvk_lstm_step_bwd")
+        fn2 = _rec_fn("hvk_lstm_step_bwd2") if D == 2 else None
+        P, PW = _r8(gh), _r8(W)
+        g_ = save.get("_gates")
+        if lstm and (g_ is None or tuple(g_.shape) != (B, T, PW) or
+                     g_.data_ptr() != save["gates"].data_ptr()):
+            raise ValueError("%s: save[\"gates\"] is not lstm_fwd's" % name)
+        # Wh^T of every direction, one copy per call
+        wt = _rec_buf(save, "_wht", (D, H, P), torch.bfloat16, dev)
+        for d, _ in dirs:
+            wt[d, :, :gh].copy_(w[d * gh:(d + 1) * gh, I:].t())
+        dg_ = _rec_buf(save, "_dg", (B, T, PW), torch.bfloat16, dev,
+                       zero=True)
+        # dc[t] = dL/dc of the chain's previous step as step t leaves it
+        dc = _rec_buf(save, "dc", (T, B, DH), torch.float32, dev) \
+            if lstm else None
+        pdg, pwt, pdc = dg_.data_ptr(), wt.data_ptr(), _p(dc)
+        ph = h_all.data_ptr()
+        pgt = g_.data_ptr() if lstm else None
+        pc = save["c"].data_ptr() if lstm else None
+        pe, lde, se = err.data_ptr(), err.stride(0), \
+            err.stride(1) if seq else 0
+        ldh, ldp = T * DH, T * PW
+
+        def step(d, rev, s):
+            t = s if rev else T - 1 - s
+            tn = t - 1 if rev else t + 1      # done one launch earlier
+            tp = t + 1 if rev else t - 1      # the chain's previous step
+            oh, og = d * H, d * gh
+            if seq:
+                e = pe + 2 * (t * se + oh)
+            else:
+                e = None if s else pe + 2 * oh
+            return (pdg + 2 * (tn * PW + og) if s else None, ldp,
+                    pwt + 2 * d * H * P, P, e, lde,
+                    pgt + 2 * (t * PW + og) if lstm else
+                    ph + 2 * (t * DH + oh), ldp if lstm else ldh,
+                    pc + 4 * (tp * DH + oh) if lstm and s < T - 1 else None,
+                    ldh, pc + 4 * (t * DH + oh) if lstm else None, ldh,
+                    pdc + 4 * (tn * B * DH + oh) if lstm and s else None, DH,
+                    pdc + 4 * (t * B * DH + oh) if lstm else None, DH,
+                    pdg + 2 * (t * PW + og), ldp)
+        _bi_steps(fn1, fn2, "hvk_lstm_step_bwd", (code, B, H), dirs, T, step,
+                  _s(x))
+        dg = dg_[:, :, :W]
+        dg2 = dg_.view(B * T, PW)[:, :W]
+    else:
+        dg = _rec_buf(save, "dg", (B, T, W), torch.float32, dev)
+        ef = err.float()
+        for d, rev in dirs:
+            wh = w.float()[d * gh:(d + 1) * gh, I:]
+            hs, gs = slice(d * H, (d + 1) * H), slice(d * gh, (d + 1) * gh)
+            dc = torch.zeros(B, H)
+            for s in range(T):
+                t = s if rev else T - 1 - s
+                tn = t - 1 if rev else t + 1
+                tp = t + 1 if rev else t - 1
+                dh = ef[:, t, hs] if seq else (ef[:, hs] if s == 0 else
+                                               torch.zeros(B, H))
+                if s:
+                    dh = dh + dg[:, tn, gs] @ wh
+                if lstm:
+                    gi, gf, gg, go = save["gates"][:, t, gs].float() \
+                        .split(H, 1)
+                    tc = torch.tanh(save["c"][:, t, hs])
+                    cp = save["c"][:, tp, hs] if s < T - 1 else \
+                        torch.zeros(B, H)
+                    dc = dc + dh * go * (1.0 - tc * tc)
+                    dg[:, t, gs] = torch.cat((dc * gg * gi * (1.0 - gi),
+                                              dc * cp * gf * (1.0 - gf),
+                                              dc * gi * (1.0 - gg * gg),
+                                              dh * tc * go * (1.0 - go)), 1)
+                    dc = dc * gf
+                else:
+                    ht = h_all[:, t, hs].float()
+                    dg[:, t, gs] = dh * (1.0 - ht * ht)
+        dg2 = dg.view(B * T, W)
+    save["dg"] = dg
+    hp = _bi_hprev(save, h_all, dirs, B, T, H).view(B * T, DH)
+    gemm(dg2, _rows(x, B, T), trans_a=True, out=dw[:, :I],
+         accumulate=accumulate, bias_grad=dbias)
+    for d, _ in dirs:
+        gemm(dg2[:, d * gh:(d + 1) * gh], hp[:, d * H:(d + 1) * H],
+             trans_a=True, out=dw[d * gh:(d + 1) * gh, I:],
+             accumulate=accumulate)
+    if not need_err_input:
+        return None
+    if err_input is None:
+        err_input = torch.empty(B, T, I, dtype=hdt, device=dev)
+    gemm(dg2, w[:, :I], out=err_input.view(B * T, I))
+    return err_input
+
+
+def _gru_fwd_dir(x, w, bias, H, return_sequences, save, out, ws, direction):
+    """gru_fwd for ``direction="reverse"`` / ``"both"``: the conventions of
+    ``_lstm_fwd_dir``; ``w`` [D*3H][I+H], ``bias`` [D*4H] = (b_r, b_z, b_n,
+    b_hn) per direction, so the projection is one GEMM per direction."""
+    name = "gru_fwd"
+    dirs = _directions(name, direction)
+    D = len(dirs)
+    B, T, I, H = _gru_args(name, x, w, bias, H, D)
+    dev = x.device
+    st = save if save is not None else (ws if ws is not None else {})
+    gh = 3 * H
+    W, DH = D * gh, D * H
+    if out is not None and not return_sequences and (
+            tuple(out.shape) != (B, DH) or out.device != dev):
+        raise ValueError("%s: out must be [%d][%d] on %s" %
+                         (name, B, DH, dev))
+    if _gpu(x):
+        fn1 = _rec_fn("hvk_gru_step_fwd")
+        fn2 = _rec_fn("hvk_gru_step_fwd2") if D == 2 else None
+        PW = _r8(W)
+        xg_ = _rec_buf(st, "_xg", (B, T, PW), torch.float32, dev)
+        h_all = _rec_buf(st, "h", (B, T, DH), torch.bfloat16, dev)
+        hf = _rec_buf(st, "hf", (B, T, DH), torch.float32, dev)
+        hn = _rec_buf(st, "hn", (B, T, DH), torch.float32, dev)
+        g_ = _rec_buf(st, "_gates", (B, T, PW), torch.bfloat16, dev) \
+            if save is not None else None
+        for d, _ in dirs:
+            gemm(_rows(x, B, T), w[d * gh:(d + 1) * gh, :I], trans_b=True,
+                 bias=None if bias is None else
+                 bias[d * 4 * H:d * 4 * H + gh],
+                 out=xg_.view(B * T, PW)[:, d * gh:(d + 1) * gh])
+        ph, phf, phn = h_all.data_ptr(), hf.data_ptr(), hn.data_ptr()
+        pxg, pg = xg_.data_ptr(), _p(g_)
+        pw, ldw = w.data_ptr() + 2 * I, w.stride(0)
+        pb = _p(bias)
+        ldh, ldp = T * DH, T * PW
+
+        def step(d, rev, s):
+            t = T - 1 - s if rev else s
+            tp = t + 1 if rev else t - 1
+            oh, og = d * H, d * gh
+            return (ph + 2 * (tp * DH + oh) if s else None, ldh,
+                    pw + 2 * og * ldw, ldw,
+                    pxg + 4 * (t * PW + og), ldp,
+                    phf + 4 * (tp * DH + oh) if s else None, ldh,
+                    phf + 4 * (t * DH + oh), ldh,
+                    phn + 4 * (t * DH + oh), ldh,
+                    ph + 2 * (t * DH + oh), ldh,
+                    pg + 2 * (t * PW + og) if pg else None, ldp,
+                    pb + 4 * (d * 4 * H + gh) if pb else None)
+        _bi_steps(fn1, fn2, "hvk_gru_step_fwd", (B, H), dirs, T, step, _s(x))
+        if save is not None:
+            save["xg"] = xg_[:, :, :W]
+            save["gates"] = g_[:, :, :W]
+    else:
+        xf, wf = x.float(), w.float()
+        xg = (xf.reshape(B * T, I) @ wf[:, :I].t()).view(B, T, W)
+        if bias is not None:
+            bf = bias.float().view(D, 4 * H)
+            xg = xg + bf[:, :gh].reshape(1, 1, W)
+        h_all = _rec_buf(st, "h", (B, T, DH), torch.float32, dev)
+        gs = save if save is not None else {}   # kept for a backward only
+        hn_all = _rec_buf(gs, "hn", (B, T, DH), torch.float32, dev)
+        gates = _rec_buf(gs, "gates", (B, T, W), torch.float32, dev)
+        for d, rev in dirs:
+            wh = wf[d * gh:(d + 1) * gh, I:]
+            bhn = torch.zeros(H) if bias is None else bf[d, gh:]
+            h = torch.zeros(B, H)
+            for s in range(T):
+                t = T - 1 - s if rev else s
+                xt = xg[:, t, d * gh:(d + 1) * gh]
+                hh = h @ wh.t() if s else torch.zeros(B, gh)
+                gr = torch.sigmoid(xt[:, :H] + hh[:, :H])
+                gz = torch.sigmoid(xt[:, H:2 * H] + hh[:, H:2 * H])
+                hn = hh[:, 2 * H:] + bhn
+                gn = torch.tanh(xt[:, 2 * H:] + gr * hn)
+                h = (1.0 - gz) * gn + gz * h
+                h_all[:, t, d * H:(d + 1) * H] = h
+                hn_all[:, t, d * H:(d + 1) * H] = hn
+                gates[:, t, d * gh:(d + 1) * gh] = torch.cat((gr, gz, gn), 1)
+        st["hf"] = h_all    # float32 already: one tensor serves both
+        if save is not None:
+            save["xg"] = xg
+    if return_sequences:
+        return h_all
+    return _bi_last(h_all, dirs, H, T, out)
+
+
+def _gru_bwd_dir(err, x, w, save, dw, dbias, accumulate, need_err_input,
+                 err_input, direction):
+    """gru_bwd for ``direction="reverse"`` / ``"both"``: the conventions of
+    ``_lstm_bwd_dir``; ``dbias`` [D*4H], the b_hn block of direction d from
+    the column sums of dGh_d's n block as in gru_bwd."""
+    name = "gru_bwd"
+    dirs = _directions(name, direction)
+    D = len(dirs)
+    if w.dim() != 2 or w.shape[0] % (3 * D):
+        raise ValueError("%s: weights %s" % (name, tuple(w.shape)))
+    B, T, I, H = _gru_args(name, x, w, None, w.shape[0] // (3 * D), D)
+    dev = x.device
+    gh = 3 * H
+    W, DH = D * gh, D * H
+    if accumulate not in (True, "overwrite"):
+        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
+                         name)
+    seq = _bi_err_check(name, err, B, T, DH, dev)
+    if dw.dtype != torch.float32 or tuple(dw.shape) != (W, I + H) or \
+            dw.stride(1) != 1 or dw.device != dev:
+        raise ValueError("%s: dw must be float32 [%d][%d] on %s" %
+                         (name, W, I + H, dev))
+    if dbias is not None and (dbias.dtype != torch.float32 or
+                              tuple(dbias.shape) != (D * 4 * H,) or
+                              not dbias.is_contiguous() or
+                              dbias.device != dev):
+        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
+                         % (name, D * 4 * H, dev))
+    hdt = torch.bfloat16 if _gpu(x) else torch.float32
+    for k, shape, dt in (("h", (B, T, DH), hdt),
+                         ("hf", (B, T, DH), torch.float32),
+                         ("hn", (B, T, DH), torch.float32),
+                         ("gates", (B, T, W), hdt)):
+        t = None if save is None else save.get(k)
+        if t is None or tuple(t.shape) != shape or t.dtype != dt or \
+                t.device != dev:
+            raise ValueError("%s: save[%r] must be %s %s from gru_fwd" %
+                             (name, k, dt, shape))
+    if need_err_input and err_input is not None and (
+            tuple(err_input.shape) != (B, T, I) or
+            not err_input.is_contiguous() or err_input.device != dev or
+            err_input.dtype != hdt):
+        raise ValueError("%s: err_input must be a contiguous %s [%d][%d][%d]"
+                         % (name, hdt, B, T, I))
+    h_all = save["h"]
+    if _gpu(x):
+        if err.dtype != torch.bfloat16:
+            raise TypeError("%s: GPU err must be bfloat16, got %s" %
+                            (name, err.dtype))
+        fn1 = _rec_fn("hvk_gru_step_bwd")
+        fn2 = _rec_fn("hvk_gru_step_bwd2") if D == 2 else None
+        P, PW = _r8(gh), _r8(W)
+        g_ = save.get("_gates")
+        if g_ is None or tuple(g_.shape) != (B, T, PW) or \
+                g_.data_ptr() != save["gates"].data_ptr():
+            raise ValueError("%s: save[\"gates\"] is not gru_fwd's" % name)
+        wt = _rec_buf(save, "_wht", (D, H, P), torch.bfloat16, dev)
+        for d, _ in dirs:
+            wt[d, :, :gh].copy_(w[d * gh:(d + 1) * gh, I:].t())
+        dgx_ = _rec_buf(save, "_dgx", (B, T, PW), torch.bfloat16, dev,
+                        zero=True)
+        dgh_ = _rec_buf(save, "_dgh", (B, T, PW), torch.bfloat16, dev,
+                        zero=True)
+        dc = _rec_buf(save, "dcarry", (T, B, DH), torch.float32, dev)
+        pdx, pdh, pwt = dgx_.data_ptr(), dgh_.data_ptr(), wt.data_ptr()
+        pdc, pgt = dc.data_ptr(), g_.data_ptr()
+        phn, phf = save["hn"].data_ptr(), save["hf"].data_ptr()
+        pe, lde, se = err.data_ptr(), err.stride(0), \
+            err.stride(1) if seq else 0
+        ldh, ldp = T * DH, T * PW
+
+        def step(d, rev, s):
+            t = s if rev else T - 1 - s
+            tn = t - 1 if rev else t + 1      # done one launch earlier
+            tp = t + 1 if rev else t - 1      # the chain's previous step
+            oh, og = d * H, d * gh
+            if seq:
+                e = pe + 2 * (t * se + oh)
+            else:
+                e = None if s else pe + 2 * oh
+            return (pdh + 2 * (tn * PW + og) if s else None, ldp,
+                    pwt + 2 * d * H * P, P, e, lde,
+                    pgt + 2 * (t * PW + og), ldp,
+                    phn + 4 * (t * DH + oh), ldh,
+                    phf + 4 * (tp * DH + oh) if s < T - 1 else None, ldh,
+                    pdc + 4 * (tn * B * DH + oh) if s else None, DH,
+                    pdc + 4 * (t * B * DH + oh), DH,
+                    pdx + 2 * (t * PW + og), ldp,
+                    pdh + 2 * (t * PW + og), ldp)
+        _bi_steps(fn1, fn2, "hvk_gru_step_bwd", (B, H), dirs, T, step, _s(x))
+        dgx, dgh = dgx_[:, :, :W], dgh_[:, :, :W]
+        dgx2 = dgx_.view(B * T, PW)[:, :W]
+        dgh2 = dgh_.view(B * T, PW)[:, :W]
+    else:
+        dgx = _rec_buf(save, "dgx", (B, T, W), torch.float32, dev)
+        dgh = _rec_buf(save, "dgh", (B, T, W), torch.float32, dev)
+        dc = _rec_buf(save, "dcarry", (T, B, DH), torch.float32, dev)
+        ef = err.float()
+        zero = torch.zeros(B, H)
+        for d, rev in dirs:
+            wh = w.float()[d * gh:(d + 1) * gh, I:]
+            hs, gs = slice(d * H, (d + 1) * H), slice(d * gh, (d + 1) * gh)
+            for s in range(T):
+                t = s if rev else T - 1 - s
+                tn = t - 1 if rev else t + 1
+                tp = t + 1 if rev else t - 1
+                dh = ef[:, t, hs] if seq else (ef[:, hs] if s == 0 else zero)
+                if s:
+                    dh = dh + dgh[:, tn, gs] @ wh + dc[tn][:, hs]
+                gr, gz, gn = save["gates"][:, t, gs].float().split(H, 1)
+                hp = save["hf"][:, tp, hs] if s < T - 1 else zero
+                dn = dh * (1.0 - gz) * (1.0 - gn * gn)
+                dz = dh * (hp - gn) * gz * (1.0 - gz)
+                dr = dn * save["hn"][:, t, hs] * gr * (1.0 - gr)
+                dgx[:, t, gs] = torch.cat((dr, dz, dn), 1)
+                dgh[:, t, gs] = torch.cat((dr, dz, dn * gr), 1)
+                dc[t][:, hs] = dh * gz
+        dgx2, dgh2 = dgx.view(B * T, W), dgh.view(B * T, W)
+    save["dgx"], save["dgh"] = dgx, dgh
+    hp = _bi_hprev(save, h_all, dirs, B, T, H).view(B * T, DH)
+    sums = None
+    if dbias is not None:
+        sums = _rec_buf(save, "_dbh", (D, gh), torch.float32, dev)
+        if accumulate is True:
+            sums.zero_()
+    for d, _ in dirs:
+        gs = slice(d * gh, (d + 1) * gh)
+        b0 = d * 4 * H
+        gemm(dgx2[:, gs], _rows(x, B, T), trans_a=True, out=dw[gs, :I],
+             accumulate=accumulate,
+             bias_grad=None if dbias is None else dbias[b0:b0 + gh])
+        # the ones column of the hidden-side GEMM sums every column of dGh;
+        # its n block is the gradient of b_hn
+        gemm(dgh2[:, gs], hp[:, d * H:(d + 1) * H], trans_a=True,
+             out=dw[gs, I:], accumulate=accumulate,
+             bias_grad=None if sums is None else sums[d])
+        if dbias is not None:
+            if accumulate is True:
+                dbias[b0 + gh:b0 + 4 * H] += sums[d, 2 * H:]
+            else:
+                dbias[b0 + gh:b0 + 4 * H].copy_(sums[d, 2 * H:])
     if not need_err_input:
         return None
     if err_input is None:

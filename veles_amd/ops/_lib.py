@@ -154,6 +154,12 @@ _OPTIONAL = {
     # s), every [B][.] operand followed by its row pitch
     "hvk_gru_step_fwd": [I, I] + [P, L] * 8 + [P, P],
     "hvk_gru_step_bwd": [I, I] + [P, L] * 10 + [P],
+    # both directions of a bidirectional layer in one launch: the operand
+    # list above once per direction (forward chain, then reverse chain)
+    "hvk_lstm_step_fwd2": [I, I, I] + [P, L] * 14 + [P],
+    "hvk_lstm_step_bwd2": [I, I, I] + [P, L] * 18 + [P],
+    "hvk_gru_step_fwd2": [I, I] + ([P, L] * 8 + [P]) * 2 + [P],
+    "hvk_gru_step_bwd2": [I, I] + [P, L] * 20 + [P],
     # restricted Boltzmann machines (csrc/kernels/rbm.hip): (transposed, n,
     # V, H, x, ldx, w, ldw, bias, probs, ldp, sample, lds, seed, seed_dev,
     # base, s); (n, V, H, splits); (n, V, H, v0, h0, vk, hk each with its
