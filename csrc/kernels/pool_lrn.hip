@@ -1629,21 +1629,6 @@ void lrn_pool3s2_bwd_dpp_kernel(
         X2[i] = f32x2_t{xv[2 * i], xv[2 * i + 1]};
         G2[i] = f32x2_t{g[p][2 * i], g[p][2 * i + 1]};
       }
-      if constexpr (AM == 1) {
-        // x is the ReLU output (>= 0): dx = 0 where x = 0 is g = 0 there
-        // (that channel's t_j = g x s^(-beta-1) is 0 anyway) - one clamped
-        // product per channel pair, min(max(x 2^126, 0), 1) = [x > 0] for
-        // every normal x, instead of a compare and a select per channel
-        // (the compiler splits a clamped vector product into two scalar
-        // v_max clamps; the packed product's clamp bit does it in one)
-        const f32x2_t BIG = {0x1p126f, 0x1p126f};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          f32x2_t m;
-          asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(m) : "v"(X2[i]), "v"(BIG));
-          G2[i] = G2[i] * m;
-        }
-      }
       // squares of channels c0 - half .. c0 + 8 + half
       float e[8 + 2 * half];
 #pragma unroll
@@ -1706,8 +1691,22 @@ void lrn_pool3s2_bwd_dpp_kernel(
       float v[8];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const f32x2_t V2 =
+        f32x2_t V2 =
             G2[i] * SB2[i] - X2[i] * f32x2_t{acc[2 * i], acc[2 * i + 1]};
+        if constexpr (AM == 1) {
+          // strict ReLU of x itself: dx = 0 where x <= 0 - one clamped
+          // product per channel pair, min(max(x 2^126, 0), 1) = [x > 0] for
+          // every normal x, instead of a compare and a select per channel
+          // (the compiler splits a clamped vector product into two scalar
+          // v_max clamps; the packed product's clamp bit does it in one).
+          // The mask is on the RESULT: the t_j of the window sum keep their
+          // unmasked gradient, so a negative x (aux = x that is no ReLU
+          // output) gives what the other paths give
+          const f32x2_t BIG = {0x1p126f, 0x1p126f};
+          f32x2_t m;
+          asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(m) : "v"(X2[i]), "v"(BIG));
+          V2 = V2 * m;
+        }
         v[2 * i] = V2.x;
         v[2 * i + 1] = V2.y;
       }
@@ -1971,12 +1970,14 @@ HVK_API int hvk_lrn_pool_bwd_u8(const void* x, const void* dp,
     const long long waves = (nblk + bpw - 1) / bpw;
     const long long blocks = std::min<long long>((waves + 3) / 4, 1 << 16);
     const bool pre = g_lrn_bwd_variant == 0;
-    // the activation derivative as a template: none, ReLU of x, any
+    // the activation derivative as a template: none, ReLU of x, any (the
+    // ReLU form only up to half = 2, AlexNet's: its mask on the result costs
+    // the wider windows their last registers - they would spill)
     const int am = !aux ? 0 : (aux == x && aux_act == ACT_STRICT_RELU) ? 1 : 2;
 #define LRN_BWD_K(H)                                                      \
     (!pre      ? lrn_pool3s2_bwd_dpp_kernel<H, false>                     \
      : am == 0 ? lrn_pool3s2_bwd_dpp_kernel<H, true, 0>                   \
-     : am == 1 ? lrn_pool3s2_bwd_dpp_kernel<H, true, 1>                   \
+     : am == 1 ? lrn_pool3s2_bwd_dpp_kernel<H, true, (H <= 2 ? 1 : 2)>    \
                : lrn_pool3s2_bwd_dpp_kernel<H, true, 2>)
     auto kd = h == 1 ? LRN_BWD_K(1) : h == 2 ? LRN_BWD_K(2)
             : h == 3 ? LRN_BWD_K(3) : LRN_BWD_K(4);

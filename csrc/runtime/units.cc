@@ -279,8 +279,12 @@ class Pooling : public Unit {
   }
   Shape OutputShape(const Shape& in) const override {
     int H = (int)in[1], W = (int)in[2];
-    size_t OH = H > ky_ ? (H - ky_ + sy_ - 1) / sy_ + 1 : 1;
-    size_t OW = W > kx_ ? (W - kx_ + sx_ - 1) / sx_ + 1 : 1;
+    // ceil, but never a window that starts outside the input (a stride above
+    // the kernel size): ops.pool_out_size
+    size_t OH = H > ky_ ? std::min((H - ky_ + sy_ - 1) / sy_,
+                                   (H - 1) / sy_) + 1 : 1;
+    size_t OW = W > kx_ ? std::min((W - kx_ + sx_ - 1) / sx_,
+                                   (W - 1) / sx_) + 1 : 1;
     return {in[0], OH, OW, in[3]};
   }
   void Execute(const Tensor& in, Tensor& out, ExecContext& ctx) override {

@@ -1405,16 +1405,25 @@ POOL = {"max": 0, "avg": 1, "maxabs": 2}
 
 def pool_out_size(h, w, ky, kx, sy, sx):
     """Znicz pooling geometry: partial windows at the far edge are kept
-    (ceil), never a window that starts outside the input."""
-    return (h - ky + sy - 1) // sy + 1 if h > ky else 1, \
-        (w - kx + sx - 1) // sx + 1 if w > kx else 1
+    (ceil), never a window that starts outside the input: with a stride
+    above the kernel size the ceil alone would count one (12 rows, 3 / 4:
+    a fourth window at row 12), so the count stops at the last start below
+    the size, (h - 1) // sy + 1.  Unchanged wherever sy <= ky: the ceil's
+    last start is then below h - ky + sy <= h."""
+    def n(size, kernel, stride):
+        if size <= kernel:
+            return 1
+        return min((size - kernel + stride - 1) // stride,
+                   (size - 1) // stride) + 1
+    return n(h, ky, sy), n(w, kx, sx)
 
 
 def _pool_ref(x, ky, kx, sy, sx, mode, OH, OW):
     N, H, W, C = x.shape
     xf = x.float()
     neg = float("-inf")
-    Hp, Wp = (OH - 1) * sy + ky, (OW - 1) * sx + kx
+    # (a stride above the kernel size can leave the last rows uncovered)
+    Hp, Wp = max(H, (OH - 1) * sy + ky), max(W, (OW - 1) * sx + kx)
     pad = torch.full((N, Hp, Wp, C), float("nan"))
     pad[:, :H, :W, :] = xf
     idx = torch.arange(N * H * W * C).view(N, H, W, C)
@@ -1499,7 +1508,8 @@ def stochastic_pool(x, ky, kx, sliding=None, use_abs=False, train=True,
     if seed_dev is not None:
         seed = int(seed_dev.reshape(-1)[0]) & 0xFFFFFFFF
     xf = x.float().cpu()
-    Hp, Wp = (OH - 1) * sy + ky, (OW - 1) * sx + kx
+    # (a stride above the kernel size can leave the last rows uncovered)
+    Hp, Wp = max(H, (OH - 1) * sy + ky), max(W, (OW - 1) * sx + kx)
     pad = torch.zeros(N, Hp, Wp, C)
     pad[:, :H, :W] = xf
     ok = torch.zeros(N, Hp, Wp, C, dtype=torch.bool)
