@@ -376,6 +376,57 @@ inline bool on_grid(const void* p, long long ld) {
   return ((uintptr_t)p & 15) == 0 && ld % 8 == 0;
 }
 
+// directions of a launch: one argument block, or a Pair of them
+template <class A>
+constexpr unsigned ndirs(const A&) { return 1; }
+template <class A>
+constexpr unsigned ndirs(const Pair<A>&) { return 2; }
+
+// Launches step kernel k on its argument block(s) over the tile grid of one
+// step: ceil(H / TH) x ceil(B / TB) x directions.  Refuses a batch with more
+// tiles than grid.y holds.
+template <class A>
+int launch_step(void (*k)(const A), const A& a, int B, int H, hipStream_t s) {
+  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB),
+                  ndirs(a));
+  if (grid.y > 65535u) return -1;
+  hipLaunchKernelGGL(k, grid, dim3(NTHR), 0, s, a);
+  return (int)launch_status(s);
+}
+
+// the step kernel that takes one argument block / a Pair of them
+template <int NG, bool VEC>
+constexpr auto fwd_kernel(const FwdArgs&) { return step_fwd_kernel<NG, VEC>; }
+template <int NG, bool VEC>
+constexpr auto fwd_kernel(const Pair<FwdArgs>&) {
+  return step_fwd2_kernel<NG, VEC>;
+}
+template <int NG, bool VEC>
+constexpr auto bwd_kernel(const BwdArgs&) { return step_bwd_kernel<NG, VEC>; }
+template <int NG, bool VEC>
+constexpr auto bwd_kernel(const Pair<BwdArgs>&) {
+  return step_bwd2_kernel<NG, VEC>;
+}
+
+// (cell, vec) -> instantiation, for one direction and for a Pair alike
+template <class A>
+int launch_fwd(const A& a, bool lstm, bool vec, int B, int H, hipStream_t s) {
+  if (lstm)
+    return vec ? launch_step(fwd_kernel<4, true>(a), a, B, H, s)
+               : launch_step(fwd_kernel<4, false>(a), a, B, H, s);
+  return vec ? launch_step(fwd_kernel<1, true>(a), a, B, H, s)
+             : launch_step(fwd_kernel<1, false>(a), a, B, H, s);
+}
+
+template <class A>
+int launch_bwd(const A& a, bool lstm, bool vec, int B, int H, hipStream_t s) {
+  if (lstm)
+    return vec ? launch_step(bwd_kernel<4, true>(a), a, B, H, s)
+               : launch_step(bwd_kernel<4, false>(a), a, B, H, s);
+  return vec ? launch_step(bwd_kernel<1, true>(a), a, B, H, s)
+             : launch_step(bwd_kernel<1, false>(a), a, B, H, s);
+}
+
 }  // namespace
 
 // One forward time step.  cell 0 (LSTM, NG = 4, gate order i f g o):
@@ -434,20 +485,7 @@ HVK_API int hvk_lstm_step_fwd(int cell, int B, int H, const void* h_prev,
   if (!fwd_args(a, vec, cell, B, H, h_prev, ld_hp, Wh, ld_w, xg, ld_xg,
                 c_prev, ld_cp, c, ld_c, h, ld_h, gates, ld_g))
     return -1;
-  const bool lstm = cell == CELL_LSTM;
-  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
-  if (grid.y > 65535u) return -1;
-#define HVK_REC_FWD(NG, VEC) \
-  hipLaunchKernelGGL((step_fwd_kernel<NG, VEC>), grid, dim3(NTHR), 0, s, a)
-  if (lstm) {
-    if (vec) HVK_REC_FWD(4, true);
-    else HVK_REC_FWD(4, false);
-  } else {
-    if (vec) HVK_REC_FWD(1, true);
-    else HVK_REC_FWD(1, false);
-  }
-#undef HVK_REC_FWD
-  return (int)launch_status(s);
+  return launch_fwd(a, cell == CELL_LSTM, vec, B, H, s);
 }
 
 // One forward time step of BOTH directions of a bidirectional layer in one
@@ -474,21 +512,7 @@ HVK_API int hvk_lstm_step_fwd2(
       !fwd_args(a1, vec1, cell, B, H, h_prev1, ld_hp1, Wh1, ld_w1, xg1,
                 ld_xg1, c_prev1, ld_cp1, c1, ld_c1, h1, ld_h1, gates1, ld_g1))
     return -1;
-  const bool lstm = cell == CELL_LSTM, vec = vec0 && vec1;
-  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB),
-                  2);
-  if (grid.y > 65535u) return -1;
-#define HVK_REC_FWD2(NG, VEC)                                                \
-  hipLaunchKernelGGL((step_fwd2_kernel<NG, VEC>), grid, dim3(NTHR), 0, s, p)
-  if (lstm) {
-    if (vec) HVK_REC_FWD2(4, true);
-    else HVK_REC_FWD2(4, false);
-  } else {
-    if (vec) HVK_REC_FWD2(1, true);
-    else HVK_REC_FWD2(1, false);
-  }
-#undef HVK_REC_FWD2
-  return (int)launch_status(s);
+  return launch_fwd(p, cell == CELL_LSTM, vec0 && vec1, B, H, s);
 }
 
 // One backward time step: dh = err + dg_next . Wh (either may be absent),
@@ -555,20 +579,7 @@ HVK_API int hvk_lstm_step_bwd(int cell, int B, int H, const void* dg_next,
                 gates, ld_g, c_prev, ld_cp, c, ld_c, dc_in, ld_dci, dc_out,
                 ld_dco, dg, ld_dg))
     return -1;
-  const bool lstm = cell == CELL_LSTM;
-  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
-  if (grid.y > 65535u) return -1;
-#define HVK_REC_BWD(NG, VEC) \
-  hipLaunchKernelGGL((step_bwd_kernel<NG, VEC>), grid, dim3(NTHR), 0, s, a)
-  if (lstm) {
-    if (vec) HVK_REC_BWD(4, true);
-    else HVK_REC_BWD(4, false);
-  } else {
-    if (vec) HVK_REC_BWD(1, true);
-    else HVK_REC_BWD(1, false);
-  }
-#undef HVK_REC_BWD
-  return (int)launch_status(s);
+  return launch_bwd(a, cell == CELL_LSTM, vec, B, H, s);
 }
 
 // One backward time step of both directions in one launch (grid.z = 2): the
@@ -596,21 +607,7 @@ HVK_API int hvk_lstm_step_bwd2(
                 ld_e1, gates1, ld_g1, c_prev1, ld_cp1, c1, ld_c1, dc_in1,
                 ld_dci1, dc_out1, ld_dco1, dg1, ld_dg1))
     return -1;
-  const bool lstm = cell == CELL_LSTM, vec = vec0 && vec1;
-  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB),
-                  2);
-  if (grid.y > 65535u) return -1;
-#define HVK_REC_BWD2(NG, VEC)                                                \
-  hipLaunchKernelGGL((step_bwd2_kernel<NG, VEC>), grid, dim3(NTHR), 0, s, p)
-  if (lstm) {
-    if (vec) HVK_REC_BWD2(4, true);
-    else HVK_REC_BWD2(4, false);
-  } else {
-    if (vec) HVK_REC_BWD2(1, true);
-    else HVK_REC_BWD2(1, false);
-  }
-#undef HVK_REC_BWD2
-  return (int)launch_status(s);
+  return launch_bwd(p, cell == CELL_LSTM, vec0 && vec1, B, H, s);
 }
 
 HVK_API int hvk_recurrent_fn(int kind, const float* x, float* y, long long n,
@@ -790,6 +787,32 @@ gru_bwd2_kernel(const Pair<GruBwdArgs> p) {
   gru_bwd_body<VEC>(p.d[blockIdx.z], red);
 }
 
+// as fwd_kernel / launch_fwd above
+template <bool VEC>
+constexpr auto gru_fwd_k(const GruFwdArgs&) { return gru_fwd_kernel<VEC>; }
+template <bool VEC>
+constexpr auto gru_fwd_k(const Pair<GruFwdArgs>&) {
+  return gru_fwd2_kernel<VEC>;
+}
+template <bool VEC>
+constexpr auto gru_bwd_k(const GruBwdArgs&) { return gru_bwd_kernel<VEC>; }
+template <bool VEC>
+constexpr auto gru_bwd_k(const Pair<GruBwdArgs>&) {
+  return gru_bwd2_kernel<VEC>;
+}
+
+template <class A>
+int launch_gru_fwd(const A& a, bool vec, int B, int H, hipStream_t s) {
+  return vec ? launch_step(gru_fwd_k<true>(a), a, B, H, s)
+             : launch_step(gru_fwd_k<false>(a), a, B, H, s);
+}
+
+template <class A>
+int launch_gru_bwd(const A& a, bool vec, int B, int H, hipStream_t s) {
+  return vec ? launch_step(gru_bwd_k<true>(a), a, B, H, s)
+             : launch_step(gru_bwd_k<false>(a), a, B, H, s);
+}
+
 }  // namespace
 
 // One forward GRU time step (equations above).  h_prev nullptr: step 0, no
@@ -845,13 +868,7 @@ HVK_API int hvk_gru_step_fwd(int B, int H, const void* h_prev,
   if (!gru_fwd_args(a, vec, B, H, h_prev, ld_hp, Wh, ld_w, xg, ld_xg, hf_prev,
                     ld_hfp, hf, ld_hf, hn, ld_hn, h, ld_h, gates, ld_g, bhn))
     return -1;
-  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
-  if (grid.y > 65535u) return -1;
-  if (vec)
-    hipLaunchKernelGGL((gru_fwd_kernel<true>), grid, dim3(NTHR), 0, s, a);
-  else
-    hipLaunchKernelGGL((gru_fwd_kernel<false>), grid, dim3(NTHR), 0, s, a);
-  return (int)launch_status(s);
+  return launch_gru_fwd(a, vec, B, H, s);
 }
 
 // One forward GRU time step of both directions in one launch (grid.z = 2):
@@ -877,14 +894,7 @@ HVK_API int hvk_gru_step_fwd2(
                     hf_prev1, ld_hfp1, hf1, ld_hf1, hn1, ld_hn1, h1, ld_h1,
                     gates1, ld_g1, bhn1))
     return -1;
-  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB),
-                  2);
-  if (grid.y > 65535u) return -1;
-  if (vec0 && vec1)
-    hipLaunchKernelGGL((gru_fwd2_kernel<true>), grid, dim3(NTHR), 0, s, p);
-  else
-    hipLaunchKernelGGL((gru_fwd2_kernel<false>), grid, dim3(NTHR), 0, s, p);
-  return (int)launch_status(s);
+  return launch_gru_fwd(p, vec0 && vec1, B, H, s);
 }
 
 // One backward GRU time step from the saved gates (r, z, n), hn and the
@@ -954,13 +964,7 @@ HVK_API int hvk_gru_step_bwd(int B, int H, const void* dgh_next,
                     gates, ld_g, hn, ld_hn, hf_prev, ld_hfp, dc_in, ld_dci,
                     dc_out, ld_dco, dgx, ld_dgx, dgh, ld_dgh))
     return -1;
-  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB));
-  if (grid.y > 65535u) return -1;
-  if (vec)
-    hipLaunchKernelGGL((gru_bwd_kernel<true>), grid, dim3(NTHR), 0, s, a);
-  else
-    hipLaunchKernelGGL((gru_bwd_kernel<false>), grid, dim3(NTHR), 0, s, a);
-  return (int)launch_status(s);
+  return launch_gru_bwd(a, vec, B, H, s);
 }
 
 // One backward GRU time step of both directions in one launch (grid.z = 2):
@@ -991,12 +995,5 @@ HVK_API int hvk_gru_step_bwd2(
                     dc_in1, ld_dci1, dc_out1, ld_dco1, dgx1, ld_dgx1, dgh1,
                     ld_dgh1))
     return -1;
-  const dim3 grid((unsigned)((H + TH - 1) / TH), (unsigned)((B + TB - 1) / TB),
-                  2);
-  if (grid.y > 65535u) return -1;
-  if (vec0 && vec1)
-    hipLaunchKernelGGL((gru_bwd2_kernel<true>), grid, dim3(NTHR), 0, s, p);
-  else
-    hipLaunchKernelGGL((gru_bwd2_kernel<false>), grid, dim3(NTHR), 0, s, p);
-  return (int)launch_status(s);
+  return launch_gru_bwd(p, vec0 && vec1, B, H, s);
 }

@@ -268,6 +268,52 @@ def test_save_none_writes_no_gates():
                        ops.gru_fwd(x, w, torch.zeros(28), 7))
 
 
+# (B, I, H, T): H = 7 is off the 8-element grid (on the GPU the scalar kernel
+# path, padded pitch != width), H = 8 is on it (the vector path)
+CONTRACT = [(3, 5, 7, 2), (2, 8, 8, 2)]
+
+
+@pytest.mark.parametrize("shape", CONTRACT, ids=("H7", "H8"))
+def test_save_contract(shape):
+    """what fwd + bwd leave in ``save`` under public keys (the table of
+    docs/OPS.md "GRU"): the tools and the tests that launch steps by hand
+    read these"""
+    B, I, H, T = shape
+    x, w, b = operands((B, T, I, H))
+    save = {}
+    ops.gru_fwd(x, w, b, H, save=save)
+    ops.gru_bwd(torch.randn(B, H), x, w, save, torch.zeros(3 * H, I + H),
+                torch.zeros(4 * H))
+    want = {"h": (B, T, H), "hf": (B, T, H), "hn": (B, T, H),
+            "gates": (B, T, 3 * H), "xg": (B, T, 3 * H),
+            "dgx": (B, T, 3 * H), "dgh": (B, T, 3 * H), "dcarry": (T, B, H)}
+    assert {k for k in save if not k.startswith("_")} == set(want)
+    for k, shape in want.items():
+        assert tuple(save[k].shape) == shape, k
+        assert save[k].dtype == torch.float32, k
+
+
+def test_forward_is_the_default_direction():
+    B, T, I, H = 3, 5, 6, 7
+    x, w, b = operands((B, T, I, H))
+    err = torch.randn(B, T, H)
+    res = []
+    for kw in ({}, {"direction": "forward"}):
+        save = {}
+        y = ops.gru_fwd(x, w, b, H, return_sequences=True, save=save, **kw)
+        dw, db = torch.zeros(3 * H, I + H), torch.zeros(4 * H)
+        ei = ops.gru_bwd(err, x, w, save, dw, db, **kw)
+        res.append((y, ei, dw, db))
+    for a, c in zip(*res):
+        assert torch.equal(a, c)
+    for bad in (lambda: ops.gru_fwd(x, w, b, H, direction="backward"),
+                lambda: ops.gru_bwd(err, x, w, save, dw, db,
+                                    direction="backward")):
+        with pytest.raises(ValueError) as e:
+            bad()
+        assert all(d in str(e.value) for d in ("forward", "reverse", "both"))
+
+
 def test_host_checks():
     x, w, b = operands((3, 5, 6, 7))
     for bad in (lambda: ops.gru_fwd(x[0], w, b, 7),

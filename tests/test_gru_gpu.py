@@ -286,6 +286,43 @@ def test_bit_identity_and_buffer_reuse():
         assert torch.equal(u, v)
 
 
+# (B, I, H, T): H = 7 is off the 8-element grid (scalar kernel path, padded
+# pitch != width), H = 8 is on it (vector path)
+CONTRACT = [(3, 5, 7, 2), (2, 8, 8, 2)]
+
+
+@pytest.mark.parametrize("shape", CONTRACT, ids=("H7", "H8"))
+def test_save_contract(shape):
+    """what fwd + bwd leave in ``save`` (the table of docs/OPS.md "GRU"): the
+    public keys with their shapes and dtypes, and the padded buffers behind
+    them"""
+    B, I, H, T = shape
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(B, T, I, generator=g).to(BF).to(DEV)
+    w = (torch.randn(3 * H, I + H, generator=g) / (I + H) ** 0.5).to(BF) \
+        .to(DEV)
+    b = torch.randn(4 * H, generator=g).to(DEV)
+    err = torch.randn(B, H, generator=g).to(BF).to(DEV)
+    save = {}
+    ops.gru_fwd(x, w, b, H, save=save)
+    ops.gru_bwd(err, x, w, save, torch.zeros(3 * H, I + H, device=DEV),
+                torch.zeros(4 * H, device=DEV))
+    torch.cuda.synchronize()
+    f32 = torch.float32
+    want = {"h": ((B, T, H), BF), "hf": ((B, T, H), f32),
+            "hn": ((B, T, H), f32), "gates": ((B, T, 3 * H), BF),
+            "xg": ((B, T, 3 * H), f32), "dgx": ((B, T, 3 * H), BF),
+            "dgh": ((B, T, 3 * H), BF), "dcarry": ((T, B, H), f32)}
+    assert {k for k in save if not k.startswith("_")} == set(want)
+    for k, (shape, dt) in want.items():
+        assert tuple(save[k].shape) == shape and save[k].dtype == dt, k
+    P = -(-3 * H // 8) * 8
+    for k in ("xg", "gates", "dgx", "dgh"):
+        assert tuple(save["_" + k].shape) == (B, T, P), k
+        assert save[k].data_ptr() == save["_" + k].data_ptr(), k
+        assert save[k].stride() == (T * P, P, 1), k
+
+
 def test_save_none_stores_no_gates_and_last_step_output():
     d = case(6)
     ws = {}

@@ -210,6 +210,58 @@ def test_save_none_writes_no_gates():
     assert ws["h"] is h       # buffers are reused
 
 
+# (B, I, H, T): H = 7 is off the 8-element grid (on the GPU the scalar kernel
+# path, padded pitch != width), H = 8 is on it (the vector path)
+CONTRACT = [(3, 5, 7, 2), (2, 8, 8, 2)]
+
+
+@pytest.mark.parametrize("cell", sorted(CELLS))
+@pytest.mark.parametrize("shape", CONTRACT, ids=("H7", "H8"))
+def test_save_contract(shape, cell):
+    """what fwd + bwd leave in ``save`` under public keys (docs/OPS.md): the
+    tools and the tests that launch steps by hand read these.  The CPU loop
+    carries dc in a local, so "dc" is a GPU key only."""
+    B, I, H, T = shape
+    ng = CELLS[cell]
+    x, w, b = operands(cell, (B, T, I, H))
+    save = {}
+    ops.lstm_fwd(x, w, b, H, cell=cell, save=save)
+    ops.lstm_bwd(torch.randn(B, H), x, w, save, torch.zeros(ng * H, I + H),
+                 torch.zeros(ng * H), cell=cell)
+    want = {"h": (B, T, H), "xg": (B, T, ng * H), "dg": (B, T, ng * H)}
+    if cell == "lstm":
+        want.update(c=(B, T, H), gates=(B, T, 4 * H))
+    assert {k for k in save if not k.startswith("_")} == set(want)
+    for k, shape in want.items():
+        assert tuple(save[k].shape) == shape, k
+        assert save[k].dtype == torch.float32, k
+
+
+@pytest.mark.parametrize("cell", sorted(CELLS))
+def test_forward_is_the_default_direction(cell):
+    B, T, I, H = 3, 5, 6, 7
+    ng = CELLS[cell]
+    x, w, b = operands(cell, (B, T, I, H))
+    err = torch.randn(B, T, H)
+    res = []
+    for kw in ({}, {"direction": "forward"}):
+        save = {}
+        y = ops.lstm_fwd(x, w, b, H, cell=cell, return_sequences=True,
+                         save=save, **kw)
+        dw, db = torch.zeros(ng * H, I + H), torch.zeros(ng * H)
+        ei = ops.lstm_bwd(err, x, w, save, dw, db, cell=cell, **kw)
+        res.append((y, ei, dw, db))
+    for a, c in zip(*res):
+        assert torch.equal(a, c)
+    for bad in (lambda: ops.lstm_fwd(x, w, b, H, cell=cell,
+                                     direction="backward"),
+                lambda: ops.lstm_bwd(err, x, w, save, dw, db, cell=cell,
+                                     direction="backward")):
+        with pytest.raises(ValueError) as e:
+            bad()
+        assert all(d in str(e.value) for d in ("forward", "reverse", "both"))
+
+
 def test_host_checks():
     x, w, b = operands("lstm", (3, 5, 6, 7))
     for bad in (lambda: ops.lstm_fwd(x[0], w, b, 7),

@@ -286,6 +286,48 @@ def test_bit_identity(cell):
         assert torch.equal(u, v)
 
 
+# (B, I, H, T): H = 7 is off the 8-element grid (scalar kernel path, padded
+# pitch != width), H = 8 is on it (vector path)
+CONTRACT = [(3, 5, 7, 2), (2, 8, 8, 2)]
+
+
+@pytest.mark.parametrize("cell", sorted(CELLS))
+@pytest.mark.parametrize("shape", CONTRACT, ids=("H7", "H8"))
+def test_save_contract(shape, cell):
+    """what fwd + bwd leave in ``save`` (docs/OPS.md): the public keys with
+    their shapes and dtypes, and the padded buffers behind them"""
+    B, I, H, T = shape
+    ng = CELLS[cell]
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(B, T, I, generator=g).to(BF).to(DEV)
+    w = (torch.randn(ng * H, I + H, generator=g) / (I + H) ** 0.5).to(BF) \
+        .to(DEV)
+    b = torch.randn(ng * H, generator=g).to(DEV)
+    err = torch.randn(B, H, generator=g).to(BF).to(DEV)
+    save = {}
+    ops.lstm_fwd(x, w, b, H, cell=cell, save=save)
+    ops.lstm_bwd(err, x, w, save, torch.zeros(ng * H, I + H, device=DEV),
+                 torch.zeros(ng * H, device=DEV), cell=cell)
+    torch.cuda.synchronize()
+    f32 = torch.float32
+    want = {"h": ((B, T, H), BF), "xg": ((B, T, ng * H), f32),
+            "dg": ((B, T, ng * H), BF)}
+    pads = ["_xg", "_dg"]
+    if cell == "lstm":
+        want.update(c=((B, T, H), f32), gates=((B, T, 4 * H), BF),
+                    dc=((T, B, H), f32))
+        pads.append("_gates")
+    assert {k for k in save if not k.startswith("_")} == set(want)
+    for k, (shape, dt) in want.items():
+        assert tuple(save[k].shape) == shape and save[k].dtype == dt, k
+    P = -(-ng * H // 8) * 8
+    for k in pads:
+        assert tuple(save[k].shape) == (B, T, P), k
+    for k in ("xg", "dg") + (("gates",) if cell == "lstm" else ()):
+        assert save[k].data_ptr() == save["_" + k].data_ptr(), k
+        assert save[k].stride() == (T * P, P, 1), k
+
+
 @pytest.mark.parametrize("last_only", (False, True))
 def test_strided_input(last_only):
     """a [B][T][.] view with a padded pitch gives the bits of a contiguous

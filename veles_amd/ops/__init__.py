@@ -2572,7 +2572,7 @@ def _rec_buf(store, key, shape, dtype, dev, zero=False):
     return t
 
 
-def _lstm_args(name, x, w, bias, H, cell, D=1):
+def _lstm_args(name, x, w, bias, H, cell, D):
     """Shared host checks of lstm_fwd / lstm_bwd over ``D`` directions;
     returns (B, T, I, H, kernel cell code, gates)."""
     if cell not in _CELLS:
@@ -2620,254 +2620,7 @@ def _rows(x, B, T):
     return x.as_strided((B * T, x.shape[2]), (x.stride(1), 1))
 
 
-def lstm_fwd(x, w, bias, H, *, cell="lstm", return_sequences=False,
-             save=None, out=None, ws=None, direction="forward"):
-    """Forward of a recurrent layer over ``x`` [B][T][I] (batch-major).
-
-    ``w`` [NG*H][I+H] is ONE parameter: ``w[:, :I]`` is Wx, ``w[:, I:]`` is
-    Wh; NG = 4 gates in the order i, f, g, o for ``cell="lstm"``, 1 for
-    ``"rnn"``; ``bias`` [NG*H] or None.  h and c start at zero.
-
-        lstm: (i, f, o) = sigmoid, g = tanh of x_t.Wx^T + bias + h_{t-1}.Wh^T
-              c_t = f c_{t-1} + i g,  h_t = o tanh(c_t)
-        rnn:  h_t = tanh(x_t.Wx^T + bias + h_{t-1}.Wh^T)
-
-    One GEMM projects all B*T rows (float32 ``xg``), then T step launches
-    run on the current stream with no host synchronisation (capturable).
-    Returns h_T [B][H], or every h_t [B][T][H] with ``return_sequences``.
-    ``save`` (a dict) receives "h" [B][T][H], "c" [B][T][H] float32, "gates"
-    [B][T][NG*H] (post-activation; lstm only) and "xg" for lstm_bwd; with
-    ``save=None`` the gates are not written.  A kept ``save`` / ``ws`` dict
-    is reused: no allocation from the second call on.
-
-    ``direction="reverse"`` / ``"both"``: see ``_lstm_fwd_dir``."""
-    name = "lstm_fwd"
-    if direction != "forward":
-        return _lstm_fwd_dir(x, w, bias, H, cell, return_sequences, save,
-                             out, ws, direction)
-    B, T, I, H, code, ng = _lstm_args(name, x, w, bias, H, cell)
-    dev = x.device
-    st = save if save is not None else (ws if ws is not None else {})
-    gh = ng * H
-    if out is not None and not return_sequences and (
-            tuple(out.shape) != (B, H) or out.device != dev):
-        raise ValueError("%s: out must be [%d][%d] on %s" % (name, B, H, dev))
-    if _gpu(x):
-        fn = _rec_fn("hvk_lstm_step_fwd")
-        P = _r8(gh)
-        xg_ = _rec_buf(st, "_xg", (B, T, P), torch.float32, dev)
-        h_all = _rec_buf(st, "h", (B, T, H), torch.bfloat16, dev)
-        lstm = ng == 4
-        c_all = _rec_buf(st, "c", (B, T, H), torch.float32, dev) \
-            if lstm else None
-        g_ = _rec_buf(st, "_gates", (B, T, P), torch.bfloat16, dev) \
-            if lstm and save is not None else None
-        gemm(_rows(x, B, T), w[:, :I], trans_b=True, bias=bias,
-             out=xg_.view(B * T, P)[:, :gh])
-        stream = _s(x)
-        ph, pc, pxg = h_all.data_ptr(), _p(c_all), xg_.data_ptr()
-        pg = _p(g_)
-        pw, ldw = w.data_ptr() + 2 * I, w.stride(0)
-        for t in range(T):
-            rc = fn(code, B, H,
-                    ph + 2 * (t - 1) * H if t else None, T * H, pw, ldw,
-                    pxg + 4 * t * P, T * P,
-                    pc + 4 * (t - 1) * H if lstm and t else None, T * H,
-                    pc + 4 * t * H if lstm else None, T * H,
-                    ph + 2 * t * H, T * H,
-                    pg + 2 * t * P if pg else None, T * P, stream)
-            if rc:
-                _lib.check(rc, "hvk_lstm_step_fwd")
-        if save is not None:
-            save["xg"] = xg_[:, :, :gh]
-            if lstm:
-                save["gates"] = g_[:, :, :gh]
-    else:
-        xf, wf = x.float(), w.float()
-        xg = xf.reshape(B * T, I) @ wf[:, :I].t()
-        if bias is not None:
-            xg = xg + bias.float().view(1, -1)
-        xg = xg.view(B, T, gh)
-        wh = wf[:, I:]
-        h_all = _rec_buf(st, "h", (B, T, H), torch.float32, dev)
-        h = torch.zeros(B, H)
-        if ng == 4:
-            c_all = _rec_buf(st, "c", (B, T, H), torch.float32, dev)
-            gates = _rec_buf(st, "gates", (B, T, gh), torch.float32, dev)
-            c = torch.zeros(B, H)
-        for t in range(T):
-            pre = xg[:, t] + h @ wh.t() if t else xg[:, t]
-            if ng == 4:
-                gi = torch.sigmoid(pre[:, :H])
-                gf = torch.sigmoid(pre[:, H:2 * H])
-                gg = torch.tanh(pre[:, 2 * H:3 * H])
-                go = torch.sigmoid(pre[:, 3 * H:])
-                c = gf * c + gi * gg
-                h = go * torch.tanh(c)
-                c_all[:, t] = c
-                gates[:, t] = torch.cat((gi, gf, gg, go), 1)
-            else:
-                h = torch.tanh(pre)
-            h_all[:, t] = h
-        if save is not None:
-            save["xg"] = xg
-    if return_sequences:
-        return h_all
-    last = h_all[:, T - 1]
-    if out is None:
-        return last.contiguous()
-    out.copy_(last)
-    return out
-
-
-def lstm_bwd(err, x, w, save, dw, dbias, *, cell="lstm", accumulate="overwrite",
-             need_err_input=True, err_input=None, direction="forward"):
-    """Backward of lstm_fwd from its ``save`` dict.
-
-    ``err`` is dL/dh_T [B][H], or dL/dh_t for every step [B][T][H] (the
-    layer ran with ``return_sequences``).  T step launches (t = T-1 .. 0)
-    fill save["dg"] = dL/d(pre-activations) [B][T][NG*H]; then
-    ``dw[:, :I]`` (+)= dG^T.X with ``dbias`` (+)= its column sums,
-    ``dw[:, I:]`` (+)= dG^T.H_prev over all B*T rows (``accumulate``: True
-    adds, "overwrite" writes, as in ``gemm``), and, with ``need_err_input``,
-    err_input [B][T][I] = dG.Wx is returned.  ``dw`` is float32 [NG*H][I+H], ``dbias`` float32 [NG*H] or
-    None.  Bit-reproducible under ``set_deterministic(True)``.
-
-    ``direction="reverse"`` / ``"both"``: see ``_lstm_bwd_dir``."""
-    name = "lstm_bwd"
-    if direction != "forward":
-        return _lstm_bwd_dir(err, x, w, save, dw, dbias, cell, accumulate,
-                             need_err_input, err_input, direction)
-    if cell not in _CELLS:
-        raise ValueError("%s: unknown cell %r (lstm, rnn)" % (name, cell))
-    ng = _CELLS[cell][1]
-    if w.dim() != 2 or w.shape[0] % ng:
-        raise ValueError("%s: weights %s" % (name, tuple(w.shape)))
-    B, T, I, H, code, ng = _lstm_args(name, x, w, None, w.shape[0] // ng,
-                                      cell)
-    dev = x.device
-    gh = ng * H
-    lstm = ng == 4
-    if accumulate not in (True, "overwrite"):
-        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
-                         name)
-    seq = err.dim() == 3
-    if tuple(err.shape) != ((B, T, H) if seq else (B, H)) or \
-            err.stride(-1) != 1 or err.device != dev:
-        raise ValueError("%s: err must be [%d][%d] or [%d][%d][%d] with "
-                         "contiguous rows on %s, got %s" %
-                         (name, B, H, B, T, H, dev, tuple(err.shape)))
-    if dw.dtype != torch.float32 or tuple(dw.shape) != (gh, I + H) or \
-            dw.stride(1) != 1 or dw.device != dev:
-        raise ValueError("%s: dw must be float32 [%d][%d] on %s" %
-                         (name, gh, I + H, dev))
-    if dbias is not None and (dbias.dtype != torch.float32 or
-                              tuple(dbias.shape) != (gh,) or
-                              not dbias.is_contiguous() or
-                              dbias.device != dev):
-        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
-                         % (name, gh, dev))
-    hdt = torch.bfloat16 if _gpu(x) else torch.float32
-    need = [("h", (B, T, H), hdt)]
-    if lstm:
-        need += [("c", (B, T, H), torch.float32), ("gates", (B, T, gh), hdt)]
-    for k, shape, dt in need:
-        t = None if save is None else save.get(k)
-        if t is None or tuple(t.shape) != shape or t.dtype != dt or \
-                t.device != dev:
-            raise ValueError("%s: save[%r] must be %s %s from lstm_fwd" %
-                             (name, k, dt, shape))
-    if need_err_input and err_input is not None and (
-            tuple(err_input.shape) != (B, T, I) or
-            not err_input.is_contiguous() or err_input.device != dev or
-            err_input.dtype != hdt):
-        raise ValueError("%s: err_input must be a contiguous %s [%d][%d][%d]"
-                         % (name, hdt, B, T, I))
-    h_all = save["h"]
-    if _gpu(x):
-        if err.dtype != torch.bfloat16:
-            raise TypeError("%s: GPU err must be bfloat16, got %s" %
-                            (name, err.dtype))
-        fn = _rec_fn("hvk_lstm_step_bwd")
-        P = _r8(gh)
-        g_ = save.get("_gates")
-        if lstm and (g_ is None or tuple(g_.shape) != (B, T, P) or
-                     g_.data_ptr() != save["gates"].data_ptr()):
-            raise ValueError("%s: save[\"gates\"] is not lstm_fwd's" % name)
-        # Wh^T, one copy per call: the product of a step sums over Wh's rows
-        wt = _rec_buf(save, "_wht", (H, P), torch.bfloat16, dev)
-        wt[:, :gh].copy_(w[:, I:].t())
-        dg_ = _rec_buf(save, "_dg", (B, T, P), torch.bfloat16, dev, zero=True)
-        # dc[t] = dL/dc_{t-1} as step t leaves it (read by step t - 1)
-        dc = _rec_buf(save, "dc", (T, B, H), torch.float32, dev) \
-            if lstm else None
-        stream = _s(x)
-        pdg, pwt, pdc = dg_.data_ptr(), wt.data_ptr(), _p(dc)
-        pgt = g_.data_ptr() if lstm else h_all.data_ptr()
-        ldgt = T * P if lstm else T * H
-        pc = save["c"].data_ptr() if lstm else None
-        pe = err.data_ptr()
-        lde = err.stride(0)
-        for t in range(T - 1, -1, -1):
-            last = t == T - 1
-            rc = fn(code, B, H,
-                    None if last else pdg + 2 * (t + 1) * P, T * P, pwt, P,
-                    pe + 2 * t * err.stride(1) if seq else
-                    (pe if last else None), lde,
-                    pgt + 2 * t * (P if lstm else H), ldgt,
-                    pc + 4 * (t - 1) * H if lstm and t else None, T * H,
-                    pc + 4 * t * H if lstm else None, T * H,
-                    None if last or not lstm else pdc + 4 * (t + 1) * B * H,
-                    H, pdc + 4 * t * B * H if lstm else None, H,
-                    pdg + 2 * t * P, T * P, stream)
-            if rc:
-                _lib.check(rc, "hvk_lstm_step_bwd")
-        dg = dg_[:, :, :gh]
-        dg2 = dg_.view(B * T, P)[:, :gh]
-    else:
-        wh = w.float()[:, I:]
-        dg = _rec_buf(save, "dg", (B, T, gh), torch.float32, dev)
-        dc = torch.zeros(B, H)
-        ef = err.float()
-        for t in range(T - 1, -1, -1):
-            dh = ef[:, t] if seq else (ef if t == T - 1 else
-                                       torch.zeros(B, H))
-            if t < T - 1:
-                dh = dh + dg[:, t + 1] @ wh
-            if lstm:
-                gi, gf, gg, go = save["gates"][:, t].float().split(H, 1)
-                tc = torch.tanh(save["c"][:, t])
-                cp = save["c"][:, t - 1] if t else torch.zeros(B, H)
-                dc = dc + dh * go * (1.0 - tc * tc)
-                dg[:, t] = torch.cat((dc * gg * gi * (1.0 - gi),
-                                      dc * cp * gf * (1.0 - gf),
-                                      dc * gi * (1.0 - gg * gg),
-                                      dh * tc * go * (1.0 - go)), 1)
-                dc = dc * gf
-            else:
-                ht = h_all[:, t].float()
-                dg[:, t] = dh * (1.0 - ht * ht)
-        dg2 = dg.view(B * T, gh)
-    save["dg"] = dg
-    # h_{t-1} of every row: h shifted by one step, zeros at t = 0
-    hp = _rec_buf(save, "_hprev", (B, T, H), hdt, dev, zero=True)
-    if T > 1:
-        hp[:, 1:].copy_(h_all[:, :T - 1])
-    gemm(dg2, _rows(x, B, T), trans_a=True, out=dw[:, :I],
-         accumulate=accumulate, bias_grad=dbias)
-    gemm(dg2, hp.view(B * T, H), trans_a=True, out=dw[:, I:],
-         accumulate=accumulate)
-    if not need_err_input:
-        return None
-    if err_input is None:
-        err_input = torch.empty(B, T, I, dtype=hdt, device=dev)
-    gemm(dg2, w[:, :I], out=err_input.view(B * T, I))
-    return err_input
-
-
-# GRU (docs/OPS.md "GRU"): gate order r, z, n; the reset gate multiplies the
-# hidden-side product only, so it has step kernels and entry points of its own.
-def _gru_args(name, x, w, bias, H, D=1):
+def _gru_args(name, x, w, bias, H, D):
     """Shared host checks of gru_fwd / gru_bwd over ``D`` directions; returns
     (B, T, I, H)."""
     H = int(H)
@@ -2908,272 +2661,15 @@ def _gru_args(name, x, w, bias, H, D=1):
     return B, T, I, H
 
 
-def gru_fwd(x, w, bias, H, *, return_sequences=False, save=None, out=None,
-            ws=None, direction="forward"):
-    """Forward of a GRU layer over ``x`` [B][T][I] (batch-major).
-
-    ``w`` [3H][I+H] is ONE parameter: ``w[:, :I]`` is Wx, ``w[:, I:]`` is Wh,
-    gate order r, z, n; ``bias`` [4H] = (b_r, b_z, b_n, b_hn) or None (torch:
-    bias_ih = bias[:3H], bias_hh = (0, 0, bias[3H:])).  h starts at zero.
-
-        r = sigmoid(x_t.Wxr^T + b_r + h_{t-1}.Whr^T)
-        z = sigmoid(x_t.Wxz^T + b_z + h_{t-1}.Whz^T)
-        hn = h_{t-1}.Whn^T + b_hn,  n = tanh(x_t.Wxn^T + b_n + r hn)
-        h_t = (1 - z) n + z h_{t-1}
-
-    One GEMM projects all B*T rows with bias[:3H] (float32 ``xg``), then T
-    step launches run on the current stream with no host synchronisation
-    (capturable).  Returns h_T [B][H], or every h_t [B][T][H] with
-    ``return_sequences``.  ``save`` (a dict) receives "h" [B][T][H], "hf" (h
-    in float32: the carry z h_{t-1} is not rounded to bf16), "hn" float32,
-    "gates" [B][T][3H] (post-activation r, z, n) and "xg" for gru_bwd; with
-    ``save=None`` the gates are not written.  A kept ``save`` / ``ws`` dict
-    is reused: no allocation from the second call on.
-
-    ``direction="reverse"`` / ``"both"``: see ``_gru_fwd_dir``."""
-    name = "gru_fwd"
-    if direction != "forward":
-        return _gru_fwd_dir(x, w, bias, H, return_sequences, save, out, ws,
-                            direction)
-    B, T, I, H = _gru_args(name, x, w, bias, H)
-    dev = x.device
-    st = save if save is not None else (ws if ws is not None else {})
-    gh = 3 * H
-    if out is not None and not return_sequences and (
-            tuple(out.shape) != (B, H) or out.device != dev):
-        raise ValueError("%s: out must be [%d][%d] on %s" % (name, B, H, dev))
-    if _gpu(x):
-        fn = _rec_fn("hvk_gru_step_fwd")
-        P = _r8(gh)
-        xg_ = _rec_buf(st, "_xg", (B, T, P), torch.float32, dev)
-        h_all = _rec_buf(st, "h", (B, T, H), torch.bfloat16, dev)
-        hf = _rec_buf(st, "hf", (B, T, H), torch.float32, dev)
-        hn = _rec_buf(st, "hn", (B, T, H), torch.float32, dev)
-        g_ = _rec_buf(st, "_gates", (B, T, P), torch.bfloat16, dev) \
-            if save is not None else None
-        gemm(_rows(x, B, T), w[:, :I], trans_b=True,
-             bias=None if bias is None else bias[:gh],
-             out=xg_.view(B * T, P)[:, :gh])
-        stream = _s(x)
-        ph, phf, phn = h_all.data_ptr(), hf.data_ptr(), hn.data_ptr()
-        pxg, pg = xg_.data_ptr(), _p(g_)
-        pw, ldw = w.data_ptr() + 2 * I, w.stride(0)
-        pbh = None if bias is None else bias.data_ptr() + 4 * gh
-        for t in range(T):
-            rc = fn(B, H,
-                    ph + 2 * (t - 1) * H if t else None, T * H, pw, ldw,
-                    pxg + 4 * t * P, T * P,
-                    phf + 4 * (t - 1) * H if t else None, T * H,
-                    phf + 4 * t * H, T * H, phn + 4 * t * H, T * H,
-                    ph + 2 * t * H, T * H,
-                    pg + 2 * t * P if pg else None, T * P, pbh, stream)
-            if rc:
-                _lib.check(rc, "hvk_gru_step_fwd")
-        if save is not None:
-            save["xg"] = xg_[:, :, :gh]
-            save["gates"] = g_[:, :, :gh]
-    else:
-        xf, wf = x.float(), w.float()
-        xg = xf.reshape(B * T, I) @ wf[:, :I].t()
-        bhn = torch.zeros(H)
-        if bias is not None:
-            xg = xg + bias.float()[:gh].view(1, -1)
-            bhn = bias.float()[gh:]
-        xg = xg.view(B, T, gh)
-        wh = wf[:, I:]
-        h_all = _rec_buf(st, "h", (B, T, H), torch.float32, dev)
-        gs = save if save is not None else {}   # kept for a backward only
-        hn_all = _rec_buf(gs, "hn", (B, T, H), torch.float32, dev)
-        gates = _rec_buf(gs, "gates", (B, T, gh), torch.float32, dev)
-        h = torch.zeros(B, H)
-        for t in range(T):
-            hh = h @ wh.t() if t else torch.zeros(B, gh)
-            gr = torch.sigmoid(xg[:, t, :H] + hh[:, :H])
-            gz = torch.sigmoid(xg[:, t, H:2 * H] + hh[:, H:2 * H])
-            hn = hh[:, 2 * H:] + bhn
-            gn = torch.tanh(xg[:, t, 2 * H:] + gr * hn)
-            h = (1.0 - gz) * gn + gz * h
-            h_all[:, t] = h
-            hn_all[:, t] = hn
-            gates[:, t] = torch.cat((gr, gz, gn), 1)
-        st["hf"] = h_all    # float32 already: one tensor serves both
-        if save is not None:
-            save["xg"] = xg
-    if return_sequences:
-        return h_all
-    last = h_all[:, T - 1]
-    if out is None:
-        return last.contiguous()
-    out.copy_(last)
-    return out
-
-
-def gru_bwd(err, x, w, save, dw, dbias, *, accumulate="overwrite",
-            need_err_input=True, err_input=None, direction="forward"):
-    """Backward of gru_fwd from its ``save`` dict.
-
-    ``err`` is dL/dh_T [B][H], or dL/dh_t for every step [B][T][H] (the
-    layer ran with ``return_sequences``).  T step launches (t = T-1 .. 0):
-
-        dh = err_t + dGh_{t+1}.Wh + dcarry_{t+1}
-        dn = dh (1 - z)(1 - n^2),  dz = dh (h_{t-1} - n) z(1 - z)
-        dr = dn hn r(1 - r)
-        dGx_t = (dr, dz, dn),  dGh_t = (dr, dz, dn r),  dcarry_t = dh z
-
-    fill save["dgx"] and save["dgh"] (two [B][T][3H] buffers: the gradient of
-    the input-side and of the hidden-side pre-activations) and
-    save["dcarry"] [T][B][H] float32; then ``dw[:, :I]`` (+)= dGx^T.X with
-    ``dbias[:3H]`` (+)= its column sums, ``dw[:, I:]`` (+)= dGh^T.H_prev with
-    ``dbias[3H:]`` (+)= the column sums of dGh[:, 2H:3H] (``accumulate``: True
-    adds, "overwrite" writes, as in ``gemm``), and, with ``need_err_input``,
-    err_input [B][T][I] = dGx.Wx is returned.  ``dw`` is float32 [3H][I+H],
-    ``dbias`` float32 [4H] or None.  Bit-reproducible under
-    ``set_deterministic(True)``.
-
-    ``direction="reverse"`` / ``"both"``: see ``_gru_bwd_dir``."""
-    name = "gru_bwd"
-    if direction != "forward":
-        return _gru_bwd_dir(err, x, w, save, dw, dbias, accumulate,
-                            need_err_input, err_input, direction)
-    if w.dim() != 2 or w.shape[0] % 3:
-        raise ValueError("%s: weights %s" % (name, tuple(w.shape)))
-    B, T, I, H = _gru_args(name, x, w, None, w.shape[0] // 3)
-    dev = x.device
-    gh = 3 * H
-    if accumulate not in (True, "overwrite"):
-        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
-                         name)
-    seq = err.dim() == 3
-    if tuple(err.shape) != ((B, T, H) if seq else (B, H)) or \
-            err.stride(-1) != 1 or err.device != dev:
-        raise ValueError("%s: err must be [%d][%d] or [%d][%d][%d] with "
-                         "contiguous rows on %s, got %s" %
-                         (name, B, H, B, T, H, dev, tuple(err.shape)))
-    if dw.dtype != torch.float32 or tuple(dw.shape) != (gh, I + H) or \
-            dw.stride(1) != 1 or dw.device != dev:
-        raise ValueError("%s: dw must be float32 [%d][%d] on %s" %
-                         (name, gh, I + H, dev))
-    if dbias is not None and (dbias.dtype != torch.float32 or
-                              tuple(dbias.shape) != (4 * H,) or
-                              not dbias.is_contiguous() or
-                              dbias.device != dev):
-        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
-                         % (name, 4 * H, dev))
-    hdt = torch.bfloat16 if _gpu(x) else torch.float32
-    for k, shape, dt in (("h", (B, T, H), hdt),
-                         ("hf", (B, T, H), torch.float32),
-                         ("hn", (B, T, H), torch.float32),
-                         ("gates", (B, T, gh), hdt)):
-        t = None if save is None else save.get(k)
-        if t is None or tuple(t.shape) != shape or t.dtype != dt or \
-                t.device != dev:
-            raise ValueError("%s: save[%r] must be %s %s from gru_fwd" %
-                             (name, k, dt, shape))
-    if need_err_input and err_input is not None and (
-            tuple(err_input.shape) != (B, T, I) or
-            not err_input.is_contiguous() or err_input.device != dev or
-            err_input.dtype != hdt):
-        raise ValueError("%s: err_input must be a contiguous %s [%d][%d][%d]"
-                         % (name, hdt, B, T, I))
-    h_all = save["h"]
-    if _gpu(x):
-        if err.dtype != torch.bfloat16:
-            raise TypeError("%s: GPU err must be bfloat16, got %s" %
-                            (name, err.dtype))
-        fn = _rec_fn("hvk_gru_step_bwd")
-        P = _r8(gh)
-        g_ = save.get("_gates")
-        if g_ is None or tuple(g_.shape) != (B, T, P) or \
-                g_.data_ptr() != save["gates"].data_ptr():
-            raise ValueError("%s: save[\"gates\"] is not gru_fwd's" % name)
-        # Wh^T, one copy per call: the product of a step sums over Wh's rows
-        wt = _rec_buf(save, "_wht", (H, P), torch.bfloat16, dev)
-        wt[:, :gh].copy_(w[:, I:].t())
-        dgx_ = _rec_buf(save, "_dgx", (B, T, P), torch.bfloat16, dev,
-                        zero=True)
-        dgh_ = _rec_buf(save, "_dgh", (B, T, P), torch.bfloat16, dev,
-                        zero=True)
-        # dcarry[t] = dh_t z_t as step t leaves it (read by step t - 1)
-        dc = _rec_buf(save, "dcarry", (T, B, H), torch.float32, dev)
-        stream = _s(x)
-        pdx, pdh, pwt = dgx_.data_ptr(), dgh_.data_ptr(), wt.data_ptr()
-        pdc, pgt = dc.data_ptr(), g_.data_ptr()
-        phn, phf = save["hn"].data_ptr(), save["hf"].data_ptr()
-        pe = err.data_ptr()
-        lde = err.stride(0)
-        for t in range(T - 1, -1, -1):
-            last = t == T - 1
-            rc = fn(B, H,
-                    None if last else pdh + 2 * (t + 1) * P, T * P, pwt, P,
-                    pe + 2 * t * err.stride(1) if seq else
-                    (pe if last else None), lde,
-                    pgt + 2 * t * P, T * P, phn + 4 * t * H, T * H,
-                    phf + 4 * (t - 1) * H if t else None, T * H,
-                    None if last else pdc + 4 * (t + 1) * B * H, H,
-                    pdc + 4 * t * B * H, H,
-                    pdx + 2 * t * P, T * P, pdh + 2 * t * P, T * P, stream)
-            if rc:
-                _lib.check(rc, "hvk_gru_step_bwd")
-        dgx, dgh = dgx_[:, :, :gh], dgh_[:, :, :gh]
-        dgx2 = dgx_.view(B * T, P)[:, :gh]
-        dgh2 = dgh_.view(B * T, P)[:, :gh]
-    else:
-        wh = w.float()[:, I:]
-        dgx = _rec_buf(save, "dgx", (B, T, gh), torch.float32, dev)
-        dgh = _rec_buf(save, "dgh", (B, T, gh), torch.float32, dev)
-        dc = _rec_buf(save, "dcarry", (T, B, H), torch.float32, dev)
-        ef = err.float()
-        zero = torch.zeros(B, H)
-        for t in range(T - 1, -1, -1):
-            dh = ef[:, t] if seq else (ef if t == T - 1 else zero)
-            if t < T - 1:
-                dh = dh + dgh[:, t + 1] @ wh + dc[t + 1]
-            gr, gz, gn = save["gates"][:, t].float().split(H, 1)
-            hp = save["hf"][:, t - 1] if t else zero
-            dn = dh * (1.0 - gz) * (1.0 - gn * gn)
-            dz = dh * (hp - gn) * gz * (1.0 - gz)
-            dr = dn * save["hn"][:, t] * gr * (1.0 - gr)
-            dgx[:, t] = torch.cat((dr, dz, dn), 1)
-            dgh[:, t] = torch.cat((dr, dz, dn * gr), 1)
-            dc[t] = dh * gz
-        dgx2, dgh2 = dgx.view(B * T, gh), dgh.view(B * T, gh)
-    save["dgx"], save["dgh"] = dgx, dgh
-    # h_{t-1} of every row: h shifted by one step, zeros at t = 0
-    hp = _rec_buf(save, "_hprev", (B, T, H), hdt, dev, zero=True)
-    if T > 1:
-        hp[:, 1:].copy_(h_all[:, :T - 1])
-    gemm(dgx2, _rows(x, B, T), trans_a=True, out=dw[:, :I],
-         accumulate=accumulate,
-         bias_grad=None if dbias is None else dbias[:gh])
-    # the ones column of the hidden-side GEMM sums every column of dGh; its
-    # n block is the gradient of b_hn
-    sums = None
-    if dbias is not None:
-        sums = _rec_buf(save, "_dbh", (gh,), torch.float32, dev)
-        if accumulate is True:
-            sums.zero_()
-    gemm(dgh2, hp.view(B * T, H), trans_a=True, out=dw[:, I:],
-         accumulate=accumulate, bias_grad=sums)
-    if dbias is not None:
-        if accumulate is True:
-            dbias[gh:] += sums[2 * H:]
-        else:
-            dbias[gh:].copy_(sums[2 * H:])
-    if not need_err_input:
-        return None
-    if err_input is None:
-        err_input = torch.empty(B, T, I, dtype=hdt, device=dev)
-    gemm(dgx2, w[:, :I], out=err_input.view(B * T, I))
-    return err_input
-
-
-# Reverse and bidirectional layers (docs/OPS.md "Bidirectional").  A direction
-# is (d, rev): its block index along every direction-major axis and whether
-# its chain runs t = T-1 .. 0.  Every wide buffer is [B][T][D*W] with
-# direction d at [..., d*W:(d+1)*W] (W = H or NG*H; the pitch of the private
-# padded ones is D*W rounded up to 8), so the kernels write both halves of
-# the [B][T][2H] output through their row pitches: no flip, no concat.
-_DIRS = {"reverse": ((0, True),), "both": ((0, False), (1, True))}
+# Directions (docs/OPS.md "Bidirectional"): every pass below is written once,
+# over a list of D = 1 or 2 directions.  A direction is (d, rev): its block
+# index along every direction-major axis and whether its chain runs
+# t = T-1 .. 0.  Every wide buffer is [B][T][D*W] with direction d at
+# [..., d*W:(d+1)*W] (W = H or NG*H; the pitch of the private padded ones is
+# D*W rounded up to 8), so the kernels write both halves of a [B][T][2H]
+# output through their row pitches: no flip, no concat.
+_DIRS = {"forward": ((0, False),), "reverse": ((0, True),),
+         "both": ((0, False), (1, True))}
 
 # "both": one paired launch per step (True) or the chain of 2T one-direction
 # launches over the same buffers (False; the A/B of tools/bench_birecurrent)
@@ -3195,24 +2691,26 @@ def _directions(name, direction):
     return _DIRS[direction]
 
 
-def _bi_steps(fn1, fn2, name, head, dirs, T, step, stream):
+def _rec_steps(fn1, fn2, name, head, dirs, T, step, stream):
     """The T step launches of one pass: ``step(d, rev, s)`` is the operand
-    list of direction (d, rev) at launch ``s`` of its chain."""
-    for s in range(T):
-        if len(dirs) == 2 and _BI_PAIRED:
-            rc = fn2(*(head + step(0, False, s) + step(1, True, s) +
-                       (stream,)))
+    list of direction (d, rev) at launch ``s`` of its chain; whatever does
+    not depend on ``s`` is the caller's to hoist out of ``step``."""
+    if len(dirs) == 2 and _BI_PAIRED:
+        for s in range(T):
+            rc = fn2(*head, *step(0, False, s), *step(1, True, s), stream)
             if rc:
                 _lib.check(rc, name + "2")
-            continue
+        return
+    for s in range(T):
         for d, rev in dirs:
-            rc = fn1(*(head + step(d, rev, s) + (stream,)))
+            rc = fn1(*head, *step(d, rev, s), stream)
             if rc:
                 _lib.check(rc, name)
 
 
-def _bi_last(h_all, dirs, H, T, out):
-    """[h^f_{T-1} | h^r_0]: the final state of every direction"""
+def _rec_last(h_all, dirs, H, T, out):
+    """The final state of every direction, [h^f_{T-1} | h^r_0] for "both",
+    into ``out`` or a new contiguous tensor"""
     if out is None:
         out = torch.empty(h_all.shape[0], len(dirs) * H, dtype=h_all.dtype,
                           device=h_all.device)
@@ -3222,7 +2720,7 @@ def _bi_last(h_all, dirs, H, T, out):
     return out
 
 
-def _bi_hprev(save, h_all, dirs, B, T, H):
+def _rec_hprev(save, h_all, dirs, B, T, H):
     """The chain's previous h of every row: h shifted by one step towards the
     chain's end, zeros at its first step (the buffer is zeroed once and those
     rows are never written)."""
@@ -3238,29 +2736,102 @@ def _bi_hprev(save, h_all, dirs, B, T, H):
     return hp
 
 
-def _bi_err_check(name, err, B, T, DH, dev):
+# Host checks that the forward passes and the backward passes of both cell
+# families share; W = D*NG*H, DH = D*H, NB = the length of the bias gradient.
+def _rec_out_check(name, out, B, DH, dev):
+    if out is not None and (tuple(out.shape) != (B, DH) or out.device != dev):
+        raise ValueError("%s: out must be [%d][%d] on %s" % (name, B, DH, dev))
+
+
+def _rec_grad_check(name, accumulate, err, dw, dbias, B, T, DH, W, K, NB, dev):
+    """``accumulate``, ``err``, ``dw`` [W][K] and ``dbias`` [NB] of a backward
+    pass; returns whether ``err`` holds every step"""
+    if accumulate not in (True, "overwrite"):
+        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
+                         name)
     seq = err.dim() == 3
     if tuple(err.shape) != ((B, T, DH) if seq else (B, DH)) or \
             err.stride(-1) != 1 or err.device != dev:
         raise ValueError("%s: err must be [%d][%d] or [%d][%d][%d] with "
                          "contiguous rows on %s, got %s" %
                          (name, B, DH, B, T, DH, dev, tuple(err.shape)))
+    if dw.dtype != torch.float32 or tuple(dw.shape) != (W, K) or \
+            dw.stride(1) != 1 or dw.device != dev:
+        raise ValueError("%s: dw must be float32 [%d][%d] on %s" %
+                         (name, W, K, dev))
+    if dbias is not None and (dbias.dtype != torch.float32 or
+                              tuple(dbias.shape) != (NB,) or
+                              not dbias.is_contiguous() or
+                              dbias.device != dev):
+        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
+                         % (name, NB, dev))
     return seq
 
 
-def _lstm_fwd_dir(x, w, bias, H, cell, return_sequences, save, out, ws,
-                  direction):
-    """lstm_fwd for ``direction="reverse"`` (D = 1: the same cell from
-    t = T-1 down to 0, h^r_t = cell(x_t, h^r_{t+1}), output aligned with the
-    input's time axis or h^r_0) and ``"both"`` (D = 2).
+def _rec_save_check(name, fwd, save, need, dev):
+    """every (key, shape, dtype) of ``need`` is in ``save`` as ``fwd`` left it"""
+    for k, shape, dt in need:
+        t = None if save is None else save.get(k)
+        if t is None or tuple(t.shape) != shape or t.dtype != dt or \
+                t.device != dev:
+            raise ValueError("%s: save[%r] must be %s %s from %s" %
+                             (name, k, dt, shape, fwd))
 
-    ``w`` [D*NG*H][I+H] and ``bias`` [D*NG*H] are direction-major, each block
-    the one-direction layout.  Returns [B][T][D*H] = [h^f_t | h^r_t] with
-    ``return_sequences``, else [B][D*H] = [h^f_{T-1} | h^r_0].  ``save`` keeps
-    the keys of lstm_fwd, every feature axis D times as wide, direction d at
-    ``[..., d*W:(d+1)*W]``.  "both" on the GPU: one projection GEMM over both
-    directions, then T paired launches on the current stream (forward chain
-    at t = s, reverse chain at t = T-1-s)."""
+
+def _rec_err_input_check(name, err_input, B, T, I, hdt, dev):
+    if err_input is not None and (
+            tuple(err_input.shape) != (B, T, I) or
+            not err_input.is_contiguous() or err_input.device != dev or
+            err_input.dtype != hdt):
+        raise ValueError("%s: err_input must be a contiguous %s [%d][%d][%d]"
+                         % (name, hdt, B, T, I))
+
+
+def _rec_err_input(err_input, dg2, w, B, T, I, hdt, dev):
+    """err_input [B][T][I] = dG.Wx, summed over the directions inside the one
+    product; into the caller's tensor or a new one"""
+    if err_input is None:
+        err_input = torch.empty(B, T, I, dtype=hdt, device=dev)
+    gemm(dg2, w[:, :I], out=err_input.view(B * T, I))
+    return err_input
+
+
+def _rec_gates_check(name, fwd, save, shape):
+    """save["_gates"] is the padded buffer that save["gates"] is a view of"""
+    g_ = save.get("_gates")
+    if g_ is None or tuple(g_.shape) != shape or \
+            g_.data_ptr() != save["gates"].data_ptr():
+        raise ValueError("%s: save[\"gates\"] is not %s's" % (name, fwd))
+    return g_
+
+
+def lstm_fwd(x, w, bias, H, *, cell="lstm", return_sequences=False,
+             save=None, out=None, ws=None, direction="forward"):
+    """Forward of a recurrent layer over ``x`` [B][T][I] (batch-major).
+
+    ``direction`` is "forward" (D = 1 direction, the chain t = 0 .. T-1),
+    "reverse" (D = 1: the same cell from t = T-1 down to 0,
+    h^r_t = cell(x_t, h^r_{t+1}), output aligned with the input's time axis)
+    or "both" (D = 2).  ``w`` [D*NG*H][I+H] and ``bias`` [D*NG*H] (or None)
+    are direction-major; each block is ONE parameter of the one-direction
+    layout: ``w[:, :I]`` is Wx, ``w[:, I:]`` is Wh; NG = 4 gates in the order
+    i, f, g, o for ``cell="lstm"``, 1 for ``"rnn"``.  h and c start at zero.
+
+        lstm: (i, f, o) = sigmoid, g = tanh of x_t.Wx^T + bias + h_{t-1}.Wh^T
+              c_t = f c_{t-1} + i g,  h_t = o tanh(c_t)
+        rnn:  h_t = tanh(x_t.Wx^T + bias + h_{t-1}.Wh^T)
+
+    One GEMM projects all B*T rows of every direction (float32 ``xg``), then
+    T step launches run on the current stream with no host synchronisation
+    (capturable); "both" advances the two chains in one paired launch per
+    step (forward chain at t = s, reverse chain at t = T-1-s).  Returns every
+    h_t [B][T][D*H] = [h^f_t | h^r_t] with ``return_sequences``, else the
+    final state of every direction [B][D*H] = [h^f_{T-1} | h^r_0] (``out``
+    when given).  ``save`` (a dict) receives "h" [B][T][D*H], "c" [B][T][D*H]
+    float32, "gates" [B][T][D*NG*H] (post-activation; lstm only) and "xg" for
+    lstm_bwd, direction d of an axis of width D*W at ``[..., d*W:(d+1)*W]``;
+    with ``save=None`` the gates are not written.  A kept ``save`` / ``ws``
+    dict is reused: no allocation from the second call on."""
     name = "lstm_fwd"
     dirs = _directions(name, direction)
     D = len(dirs)
@@ -3268,19 +2839,17 @@ def _lstm_fwd_dir(x, w, bias, H, cell, return_sequences, save, out, ws,
     dev = x.device
     st = save if save is not None else (ws if ws is not None else {})
     gh = ng * H
-    W = D * gh
+    W, DH = D * gh, D * H
     lstm = ng == 4
-    if out is not None and not return_sequences and (
-            tuple(out.shape) != (B, D * H) or out.device != dev):
-        raise ValueError("%s: out must be [%d][%d] on %s" %
-                         (name, B, D * H, dev))
+    if not return_sequences:
+        _rec_out_check(name, out, B, DH, dev)
     if _gpu(x):
         fn1 = _rec_fn("hvk_lstm_step_fwd")
         fn2 = _rec_fn("hvk_lstm_step_fwd2") if D == 2 else None
         PW = _r8(W)
         xg_ = _rec_buf(st, "_xg", (B, T, PW), torch.float32, dev)
-        h_all = _rec_buf(st, "h", (B, T, D * H), torch.bfloat16, dev)
-        c_all = _rec_buf(st, "c", (B, T, D * H), torch.float32, dev) \
+        h_all = _rec_buf(st, "h", (B, T, DH), torch.bfloat16, dev)
+        c_all = _rec_buf(st, "c", (B, T, DH), torch.float32, dev) \
             if lstm else None
         g_ = _rec_buf(st, "_gates", (B, T, PW), torch.bfloat16, dev) \
             if lstm and save is not None else None
@@ -3288,22 +2857,20 @@ def _lstm_fwd_dir(x, w, bias, H, cell, return_sequences, save, out, ws,
              out=xg_.view(B * T, PW)[:, :W])
         ph, pc, pxg = h_all.data_ptr(), _p(c_all), xg_.data_ptr()
         pg = _p(g_)
-        pw, ldw = w.data_ptr() + 2 * I, w.stride(0)
-        DH, ldh, ldp = D * H, T * D * H, T * PW
+        ldw, ldh, ldp = w.stride(0), T * DH, T * PW
+        pw = [w.data_ptr() + 2 * (I + d * gh * ldw) for d in range(D)]
 
         def step(d, rev, s):
             t = T - 1 - s if rev else s
-            tp = t + 1 if rev else t - 1
-            oh, og = d * H, d * gh
-            return (ph + 2 * (tp * DH + oh) if s else None, ldh,
-                    pw + 2 * og * ldw, ldw,
-                    pxg + 4 * (t * PW + og), ldp,
-                    pc + 4 * (tp * DH + oh) if lstm and s else None, ldh,
-                    pc + 4 * (t * DH + oh) if lstm else None, ldh,
-                    ph + 2 * (t * DH + oh), ldh,
-                    pg + 2 * (t * PW + og) if pg else None, ldp)
-        _bi_steps(fn1, fn2, "hvk_lstm_step_fwd", (code, B, H), dirs, T, step,
-                  _s(x))
+            a, ag = t * DH + d * H, t * PW + d * gh     # row t of direction d
+            ap = a + DH if rev else a - DH              # the chain's previous
+            return (ph + 2 * ap if s else None, ldh, pw[d], ldw,
+                    pxg + 4 * ag, ldp,
+                    pc + 4 * ap if lstm and s else None, ldh,
+                    pc + 4 * a if lstm else None, ldh, ph + 2 * a, ldh,
+                    pg + 2 * ag if pg else None, ldp)
+        _rec_steps(fn1, fn2, "hvk_lstm_step_fwd", (code, B, H), dirs, T, step,
+                   _s(x))
         if save is not None:
             save["xg"] = xg_[:, :, :W]
             if lstm:
@@ -3314,9 +2881,9 @@ def _lstm_fwd_dir(x, w, bias, H, cell, return_sequences, save, out, ws,
         if bias is not None:
             xg = xg + bias.float().view(1, -1)
         xg = xg.view(B, T, W)
-        h_all = _rec_buf(st, "h", (B, T, D * H), torch.float32, dev)
+        h_all = _rec_buf(st, "h", (B, T, DH), torch.float32, dev)
         if lstm:
-            c_all = _rec_buf(st, "c", (B, T, D * H), torch.float32, dev)
+            c_all = _rec_buf(st, "c", (B, T, DH), torch.float32, dev)
             gates = _rec_buf(st, "gates", (B, T, W), torch.float32, dev)
         for d, rev in dirs:
             wh = wf[d * gh:(d + 1) * gh, I:]
@@ -3344,21 +2911,29 @@ def _lstm_fwd_dir(x, w, bias, H, cell, return_sequences, save, out, ws,
             save["xg"] = xg
     if return_sequences:
         return h_all
-    return _bi_last(h_all, dirs, H, T, out)
+    return _rec_last(h_all, dirs, H, T, out)
 
 
-def _lstm_bwd_dir(err, x, w, save, dw, dbias, cell, accumulate,
-                  need_err_input, err_input, direction):
-    """lstm_bwd for ``direction="reverse"`` / ``"both"``.
+def lstm_bwd(err, x, w, save, dw, dbias, *, cell="lstm", accumulate="overwrite",
+             need_err_input=True, err_input=None, direction="forward"):
+    """Backward of lstm_fwd from its ``save`` dict, with its ``direction``.
 
-    ``err`` is [B][T][D*H], or [B][D*H] = the error of [h^f_{T-1} | h^r_0]:
-    its first half enters the forward chain at t = T-1, its second half the
-    reverse chain at t = 0.  The backward walks every chain from its end
-    ("both": one paired launch per step, forward chain at t = T-1-s, reverse
-    chain at t = s).  The weight rows of direction d take dG_d^T.X and
-    dG_d^T.Hprev_d (Hprev_f[t] = h^f_{t-1}, Hprev_r[t] = h^r_{t+1}, zero at
-    the chain's first step); ``dbias`` is direction-major; err_input =
-    sum_d dG_d.Wx_d is ONE GEMM over K = D*NG*H (no atomic accumulation)."""
+    ``err`` is dL/dh_t for every step [B][T][D*H] (the layer ran with
+    ``return_sequences``), or [B][D*H] = the error of the final states
+    [h^f_{T-1} | h^r_0]: the block of a forward chain enters at t = T-1, that
+    of a reverse chain at t = 0.  T step launches walk every chain from its
+    end (forward chain t = T-1 .. 0, reverse chain t = 0 .. T-1; "both": one
+    paired launch per step) and fill save["dg"] = dL/d(pre-activations)
+    [B][T][D*NG*H] (and save["dc"] [T][B][D*H] float32 on the GPU); then
+    ``dw[:, :I]`` (+)= dG^T.X with ``dbias`` (+)= its column sums, the rows
+    of direction d of ``dw[:, I:]`` (+)= dG_d^T.Hprev_d over all B*T rows
+    (Hprev_f[t] = h^f_{t-1}, Hprev_r[t] = h^r_{t+1}, zero at the chain's first
+    step; ``accumulate``: True adds, "overwrite" writes, as in ``gemm``), and,
+    with ``need_err_input``, err_input [B][T][I] = sum_d dG_d.Wx_d is
+    returned: ONE GEMM over K = D*NG*H, no atomic accumulation.  ``dw`` is
+    float32 [D*NG*H][I+H], ``dbias`` float32 [D*NG*H] or None, both
+    direction-major as ``w`` and ``bias``.  Bit-reproducible under
+    ``set_deterministic(True)``."""
     name = "lstm_bwd"
     dirs = _directions(name, direction)
     D = len(dirs)
@@ -3371,39 +2946,17 @@ def _lstm_bwd_dir(err, x, w, save, dw, dbias, cell, accumulate,
                                       w.shape[0] // (D * ng), cell, D)
     dev = x.device
     gh = ng * H
-    W = D * gh
-    DH = D * H
+    W, DH = D * gh, D * H
     lstm = ng == 4
-    if accumulate not in (True, "overwrite"):
-        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
-                         name)
-    seq = _bi_err_check(name, err, B, T, DH, dev)
-    if dw.dtype != torch.float32 or tuple(dw.shape) != (W, I + H) or \
-            dw.stride(1) != 1 or dw.device != dev:
-        raise ValueError("%s: dw must be float32 [%d][%d] on %s" %
-                         (name, W, I + H, dev))
-    if dbias is not None and (dbias.dtype != torch.float32 or
-                              tuple(dbias.shape) != (W,) or
-                              not dbias.is_contiguous() or
-                              dbias.device != dev):
-        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
-                         % (name, W, dev))
+    seq = _rec_grad_check(name, accumulate, err, dw, dbias, B, T, DH, W,
+                          I + H, W, dev)
     hdt = torch.bfloat16 if _gpu(x) else torch.float32
     need = [("h", (B, T, DH), hdt)]
     if lstm:
         need += [("c", (B, T, DH), torch.float32), ("gates", (B, T, W), hdt)]
-    for k, shape, dt in need:
-        t = None if save is None else save.get(k)
-        if t is None or tuple(t.shape) != shape or t.dtype != dt or \
-                t.device != dev:
-            raise ValueError("%s: save[%r] must be %s %s from lstm_fwd" %
-                             (name, k, dt, shape))
-    if need_err_input and err_input is not None and (
-            tuple(err_input.shape) != (B, T, I) or
-            not err_input.is_contiguous() or err_input.device != dev or
-            err_input.dtype != hdt):
-        raise ValueError("%s: err_input must be a contiguous %s [%d][%d][%d]"
-                         % (name, hdt, B, T, I))
+    _rec_save_check(name, "lstm_fwd", save, need, dev)
+    if need_err_input:
+        _rec_err_input_check(name, err_input, B, T, I, hdt, dev)
     h_all = save["h"]
     if _gpu(x):
         if err.dtype != torch.bfloat16:
@@ -3412,11 +2965,10 @@ def _lstm_bwd_dir(err, x, w, save, dw, dbias, cell, accumulate,
         fn1 = _rec_fn("hvk_lstm_step_bwd")
         fn2 = _rec_fn("hvk_lstm_step_bwd2") if D == 2 else None
         P, PW = _r8(gh), _r8(W)
-        g_ = save.get("_gates")
-        if lstm and (g_ is None or tuple(g_.shape) != (B, T, PW) or
-                     g_.data_ptr() != save["gates"].data_ptr()):
-            raise ValueError("%s: save[\"gates\"] is not lstm_fwd's" % name)
-        # Wh^T of every direction, one copy per call
+        if lstm:
+            g_ = _rec_gates_check(name, "lstm_fwd", save, (B, T, PW))
+        # Wh^T of every direction, one copy per call: the product of a step
+        # sums over Wh's rows
         wt = _rec_buf(save, "_wht", (D, H, P), torch.bfloat16, dev)
         for d, _ in dirs:
             wt[d, :, :gh].copy_(w[d * gh:(d + 1) * gh, I:].t())
@@ -3425,34 +2977,34 @@ def _lstm_bwd_dir(err, x, w, save, dw, dbias, cell, accumulate,
         # dc[t] = dL/dc of the chain's previous step as step t leaves it
         dc = _rec_buf(save, "dc", (T, B, DH), torch.float32, dev) \
             if lstm else None
-        pdg, pwt, pdc = dg_.data_ptr(), wt.data_ptr(), _p(dc)
-        ph = h_all.data_ptr()
-        pgt = g_.data_ptr() if lstm else None
+        pdg, pdc = dg_.data_ptr(), _p(dc)
+        pwt = [wt.data_ptr() + 2 * d * H * P for d in range(D)]
+        # what the step reads as "gates": the saved gates, RNN: h itself
+        pgt, ldg = (g_.data_ptr(), T * PW) if lstm else \
+            (h_all.data_ptr(), T * DH)
         pc = save["c"].data_ptr() if lstm else None
         pe, lde, se = err.data_ptr(), err.stride(0), \
             err.stride(1) if seq else 0
-        ldh, ldp = T * DH, T * PW
+        ldh, ldp, BDH = T * DH, T * PW, B * DH
 
         def step(d, rev, s):
             t = s if rev else T - 1 - s
-            tn = t - 1 if rev else t + 1      # done one launch earlier
-            tp = t + 1 if rev else t - 1      # the chain's previous step
-            oh, og = d * H, d * gh
+            k = 1 if rev else -1      # towards the chain's previous step
+            oh = d * H
+            a, ag, ac = t * DH + oh, t * PW + d * gh, t * BDH + oh
             if seq:
                 e = pe + 2 * (t * se + oh)
             else:
                 e = None if s else pe + 2 * oh
-            return (pdg + 2 * (tn * PW + og) if s else None, ldp,
-                    pwt + 2 * d * H * P, P, e, lde,
-                    pgt + 2 * (t * PW + og) if lstm else
-                    ph + 2 * (t * DH + oh), ldp if lstm else ldh,
-                    pc + 4 * (tp * DH + oh) if lstm and s < T - 1 else None,
-                    ldh, pc + 4 * (t * DH + oh) if lstm else None, ldh,
-                    pdc + 4 * (tn * B * DH + oh) if lstm and s else None, DH,
-                    pdc + 4 * (t * B * DH + oh) if lstm else None, DH,
-                    pdg + 2 * (t * PW + og), ldp)
-        _bi_steps(fn1, fn2, "hvk_lstm_step_bwd", (code, B, H), dirs, T, step,
-                  _s(x))
+            # the step done one launch earlier is at t - k
+            return (pdg + 2 * (ag - k * PW) if s else None, ldp, pwt[d], P,
+                    e, lde, pgt + 2 * (ag if lstm else a), ldg,
+                    pc + 4 * (a + k * DH) if lstm and s < T - 1 else None,
+                    ldh, pc + 4 * a if lstm else None, ldh,
+                    pdc + 4 * (ac - k * BDH) if lstm and s else None, DH,
+                    pdc + 4 * ac if lstm else None, DH, pdg + 2 * ag, ldp)
+        _rec_steps(fn1, fn2, "hvk_lstm_step_bwd", (code, B, H), dirs, T, step,
+                   _s(x))
         dg = dg_[:, :, :W]
         dg2 = dg_.view(B * T, PW)[:, :W]
     else:
@@ -3487,25 +3039,45 @@ def _lstm_bwd_dir(err, x, w, save, dw, dbias, cell, accumulate,
                     dg[:, t, gs] = dh * (1.0 - ht * ht)
         dg2 = dg.view(B * T, W)
     save["dg"] = dg
-    hp = _bi_hprev(save, h_all, dirs, B, T, H).view(B * T, DH)
+    hp = _rec_hprev(save, h_all, dirs, B, T, H).view(B * T, DH)
     gemm(dg2, _rows(x, B, T), trans_a=True, out=dw[:, :I],
          accumulate=accumulate, bias_grad=dbias)
     for d, _ in dirs:
         gemm(dg2[:, d * gh:(d + 1) * gh], hp[:, d * H:(d + 1) * H],
              trans_a=True, out=dw[d * gh:(d + 1) * gh, I:],
              accumulate=accumulate)
-    if not need_err_input:
-        return None
-    if err_input is None:
-        err_input = torch.empty(B, T, I, dtype=hdt, device=dev)
-    gemm(dg2, w[:, :I], out=err_input.view(B * T, I))
-    return err_input
+    return _rec_err_input(err_input, dg2, w, B, T, I, hdt, dev) \
+        if need_err_input else None
 
 
-def _gru_fwd_dir(x, w, bias, H, return_sequences, save, out, ws, direction):
-    """gru_fwd for ``direction="reverse"`` / ``"both"``: the conventions of
-    ``_lstm_fwd_dir``; ``w`` [D*3H][I+H], ``bias`` [D*4H] = (b_r, b_z, b_n,
-    b_hn) per direction, so the projection is one GEMM per direction."""
+# GRU (docs/OPS.md "GRU"): gate order r, z, n; the reset gate multiplies the
+# hidden-side product only, so it has step kernels and entry points of its own.
+def gru_fwd(x, w, bias, H, *, return_sequences=False, save=None, out=None,
+            ws=None, direction="forward"):
+    """Forward of a GRU layer over ``x`` [B][T][I] (batch-major).
+
+    ``direction`` ("forward", "reverse", "both"), D, the direction-major
+    layout, the returned tensor and ``out`` are those of ``lstm_fwd``.  ``w``
+    [D*3H][I+H]: per direction ONE parameter, ``w[:, :I]`` is Wx, ``w[:, I:]``
+    is Wh, gate order r, z, n; ``bias`` [D*4H] = (b_r, b_z, b_n, b_hn) per
+    direction, or None (torch: bias_ih = the block's [:3H], bias_hh = (0, 0,
+    its [3H:])).  h starts at zero; h_{t-1} is the chain's previous step.
+
+        r = sigmoid(x_t.Wxr^T + b_r + h_{t-1}.Whr^T)
+        z = sigmoid(x_t.Wxz^T + b_z + h_{t-1}.Whz^T)
+        hn = h_{t-1}.Whn^T + b_hn,  n = tanh(x_t.Wxn^T + b_n + r hn)
+        h_t = (1 - z) n + z h_{t-1}
+
+    One GEMM per direction (the [4H] bias blocks are not contiguous over the
+    directions) projects all B*T rows with the block's bias[:3H] (float32
+    ``xg``), then T step launches run on the current stream with no host
+    synchronisation (capturable), paired for "both".  ``save`` (a dict)
+    receives "h" [B][T][D*H], "hf" (h in float32: the carry z h_{t-1} is not
+    rounded to bf16), "hn" float32, "gates" [B][T][D*3H] (post-activation r,
+    z, n) and "xg" for gru_bwd, direction d of an axis of width D*W at
+    ``[..., d*W:(d+1)*W]``; with ``save=None`` the gates are not written.  A
+    kept ``save`` / ``ws`` dict is reused: no allocation from the second call
+    on."""
     name = "gru_fwd"
     dirs = _directions(name, direction)
     D = len(dirs)
@@ -3514,10 +3086,8 @@ def _gru_fwd_dir(x, w, bias, H, return_sequences, save, out, ws, direction):
     st = save if save is not None else (ws if ws is not None else {})
     gh = 3 * H
     W, DH = D * gh, D * H
-    if out is not None and not return_sequences and (
-            tuple(out.shape) != (B, DH) or out.device != dev):
-        raise ValueError("%s: out must be [%d][%d] on %s" %
-                         (name, B, DH, dev))
+    if not return_sequences:
+        _rec_out_check(name, out, B, DH, dev)
     if _gpu(x):
         fn1 = _rec_fn("hvk_gru_step_fwd")
         fn2 = _rec_fn("hvk_gru_step_fwd2") if D == 2 else None
@@ -3535,24 +3105,20 @@ def _gru_fwd_dir(x, w, bias, H, return_sequences, save, out, ws, direction):
                  out=xg_.view(B * T, PW)[:, d * gh:(d + 1) * gh])
         ph, phf, phn = h_all.data_ptr(), hf.data_ptr(), hn.data_ptr()
         pxg, pg = xg_.data_ptr(), _p(g_)
-        pw, ldw = w.data_ptr() + 2 * I, w.stride(0)
-        pb = _p(bias)
-        ldh, ldp = T * DH, T * PW
+        ldw, ldh, ldp = w.stride(0), T * DH, T * PW
+        pw = [w.data_ptr() + 2 * (I + d * gh * ldw) for d in range(D)]
+        pb = [None if bias is None else bias.data_ptr() + 4 * (d * 4 * H + gh)
+              for d in range(D)]
 
         def step(d, rev, s):
             t = T - 1 - s if rev else s
-            tp = t + 1 if rev else t - 1
-            oh, og = d * H, d * gh
-            return (ph + 2 * (tp * DH + oh) if s else None, ldh,
-                    pw + 2 * og * ldw, ldw,
-                    pxg + 4 * (t * PW + og), ldp,
-                    phf + 4 * (tp * DH + oh) if s else None, ldh,
-                    phf + 4 * (t * DH + oh), ldh,
-                    phn + 4 * (t * DH + oh), ldh,
-                    ph + 2 * (t * DH + oh), ldh,
-                    pg + 2 * (t * PW + og) if pg else None, ldp,
-                    pb + 4 * (d * 4 * H + gh) if pb else None)
-        _bi_steps(fn1, fn2, "hvk_gru_step_fwd", (B, H), dirs, T, step, _s(x))
+            a, ag = t * DH + d * H, t * PW + d * gh     # row t of direction d
+            ap = a + DH if rev else a - DH              # the chain's previous
+            return (ph + 2 * ap if s else None, ldh, pw[d], ldw,
+                    pxg + 4 * ag, ldp, phf + 4 * ap if s else None, ldh,
+                    phf + 4 * a, ldh, phn + 4 * a, ldh, ph + 2 * a, ldh,
+                    pg + 2 * ag if pg else None, ldp, pb[d])
+        _rec_steps(fn1, fn2, "hvk_gru_step_fwd", (B, H), dirs, T, step, _s(x))
         if save is not None:
             save["xg"] = xg_[:, :, :W]
             save["gates"] = g_[:, :, :W]
@@ -3587,14 +3153,32 @@ def _gru_fwd_dir(x, w, bias, H, return_sequences, save, out, ws, direction):
             save["xg"] = xg
     if return_sequences:
         return h_all
-    return _bi_last(h_all, dirs, H, T, out)
+    return _rec_last(h_all, dirs, H, T, out)
 
 
-def _gru_bwd_dir(err, x, w, save, dw, dbias, accumulate, need_err_input,
-                 err_input, direction):
-    """gru_bwd for ``direction="reverse"`` / ``"both"``: the conventions of
-    ``_lstm_bwd_dir``; ``dbias`` [D*4H], the b_hn block of direction d from
-    the column sums of dGh_d's n block as in gru_bwd."""
+def gru_bwd(err, x, w, save, dw, dbias, *, accumulate="overwrite",
+            need_err_input=True, err_input=None, direction="forward"):
+    """Backward of gru_fwd from its ``save`` dict, with its ``direction``.
+
+    ``err``, the walk of every chain from its end, Hprev_d, ``accumulate``
+    and the direction-major ``dw`` [D*3H][I+H] are those of ``lstm_bwd``.  A
+    step, with "next" the step done one launch earlier (t + 1 on a forward
+    chain, t - 1 on a reverse one):
+
+        dh = err_t + dGh_next.Wh + dcarry_next
+        dn = dh (1 - z)(1 - n^2),  dz = dh (h_{t-1} - n) z(1 - z)
+        dr = dn hn r(1 - r)
+        dGx_t = (dr, dz, dn),  dGh_t = (dr, dz, dn r),  dcarry_t = dh z
+
+    The steps fill save["dgx"] and save["dgh"] (two [B][T][D*3H] buffers: the
+    gradient of the input-side and of the hidden-side pre-activations) and
+    save["dcarry"] [T][B][D*H] float32; then, per direction d, its rows of
+    ``dw[:, :I]`` (+)= dGx_d^T.X with the [:3H] of its ``dbias`` block (+)=
+    the column sums, its rows of ``dw[:, I:]`` (+)= dGh_d^T.Hprev_d with the
+    [3H:] of its ``dbias`` block (+)= the column sums of dGh_d's n block,
+    and, with ``need_err_input``, err_input [B][T][I] = sum_d dGx_d.Wx_d (one
+    GEMM) is returned.  ``dbias`` is float32 [D*4H] or None.
+    Bit-reproducible under ``set_deterministic(True)``."""
     name = "gru_bwd"
     dirs = _directions(name, direction)
     D = len(dirs)
@@ -3604,36 +3188,15 @@ def _gru_bwd_dir(err, x, w, save, dw, dbias, accumulate, need_err_input,
     dev = x.device
     gh = 3 * H
     W, DH = D * gh, D * H
-    if accumulate not in (True, "overwrite"):
-        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
-                         name)
-    seq = _bi_err_check(name, err, B, T, DH, dev)
-    if dw.dtype != torch.float32 or tuple(dw.shape) != (W, I + H) or \
-            dw.stride(1) != 1 or dw.device != dev:
-        raise ValueError("%s: dw must be float32 [%d][%d] on %s" %
-                         (name, W, I + H, dev))
-    if dbias is not None and (dbias.dtype != torch.float32 or
-                              tuple(dbias.shape) != (D * 4 * H,) or
-                              not dbias.is_contiguous() or
-                              dbias.device != dev):
-        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
-                         % (name, D * 4 * H, dev))
+    seq = _rec_grad_check(name, accumulate, err, dw, dbias, B, T, DH, W,
+                          I + H, D * 4 * H, dev)
     hdt = torch.bfloat16 if _gpu(x) else torch.float32
-    for k, shape, dt in (("h", (B, T, DH), hdt),
-                         ("hf", (B, T, DH), torch.float32),
-                         ("hn", (B, T, DH), torch.float32),
-                         ("gates", (B, T, W), hdt)):
-        t = None if save is None else save.get(k)
-        if t is None or tuple(t.shape) != shape or t.dtype != dt or \
-                t.device != dev:
-            raise ValueError("%s: save[%r] must be %s %s from gru_fwd" %
-                             (name, k, dt, shape))
-    if need_err_input and err_input is not None and (
-            tuple(err_input.shape) != (B, T, I) or
-            not err_input.is_contiguous() or err_input.device != dev or
-            err_input.dtype != hdt):
-        raise ValueError("%s: err_input must be a contiguous %s [%d][%d][%d]"
-                         % (name, hdt, B, T, I))
+    _rec_save_check(name, "gru_fwd", save,
+                    (("h", (B, T, DH), hdt), ("hf", (B, T, DH), torch.float32),
+                     ("hn", (B, T, DH), torch.float32),
+                     ("gates", (B, T, W), hdt)), dev)
+    if need_err_input:
+        _rec_err_input_check(name, err_input, B, T, I, hdt, dev)
     h_all = save["h"]
     if _gpu(x):
         if err.dtype != torch.bfloat16:
@@ -3642,10 +3205,9 @@ def _gru_bwd_dir(err, x, w, save, dw, dbias, accumulate, need_err_input,
         fn1 = _rec_fn("hvk_gru_step_bwd")
         fn2 = _rec_fn("hvk_gru_step_bwd2") if D == 2 else None
         P, PW = _r8(gh), _r8(W)
-        g_ = save.get("_gates")
-        if g_ is None or tuple(g_.shape) != (B, T, PW) or \
-                g_.data_ptr() != save["gates"].data_ptr():
-            raise ValueError("%s: save[\"gates\"] is not gru_fwd's" % name)
+        g_ = _rec_gates_check(name, "gru_fwd", save, (B, T, PW))
+        # Wh^T of every direction, one copy per call: the product of a step
+        # sums over Wh's rows
         wt = _rec_buf(save, "_wht", (D, H, P), torch.bfloat16, dev)
         for d, _ in dirs:
             wt[d, :, :gh].copy_(w[d * gh:(d + 1) * gh, I:].t())
@@ -3653,33 +3215,33 @@ def _gru_bwd_dir(err, x, w, save, dw, dbias, accumulate, need_err_input,
                         zero=True)
         dgh_ = _rec_buf(save, "_dgh", (B, T, PW), torch.bfloat16, dev,
                         zero=True)
+        # dcarry[t] = dh_t z_t as step t leaves it (read by the chain's
+        # previous step)
         dc = _rec_buf(save, "dcarry", (T, B, DH), torch.float32, dev)
-        pdx, pdh, pwt = dgx_.data_ptr(), dgh_.data_ptr(), wt.data_ptr()
-        pdc, pgt = dc.data_ptr(), g_.data_ptr()
-        phn, phf = save["hn"].data_ptr(), save["hf"].data_ptr()
+        pdx, pdh, pdc = dgx_.data_ptr(), dgh_.data_ptr(), dc.data_ptr()
+        pwt = [wt.data_ptr() + 2 * d * H * P for d in range(D)]
+        pgt, phn = g_.data_ptr(), save["hn"].data_ptr()
+        phf = save["hf"].data_ptr()
         pe, lde, se = err.data_ptr(), err.stride(0), \
             err.stride(1) if seq else 0
-        ldh, ldp = T * DH, T * PW
+        ldh, ldp, BDH = T * DH, T * PW, B * DH
 
         def step(d, rev, s):
             t = s if rev else T - 1 - s
-            tn = t - 1 if rev else t + 1      # done one launch earlier
-            tp = t + 1 if rev else t - 1      # the chain's previous step
-            oh, og = d * H, d * gh
+            k = 1 if rev else -1      # towards the chain's previous step
+            oh = d * H
+            a, ag, ac = t * DH + oh, t * PW + d * gh, t * BDH + oh
             if seq:
                 e = pe + 2 * (t * se + oh)
             else:
                 e = None if s else pe + 2 * oh
-            return (pdh + 2 * (tn * PW + og) if s else None, ldp,
-                    pwt + 2 * d * H * P, P, e, lde,
-                    pgt + 2 * (t * PW + og), ldp,
-                    phn + 4 * (t * DH + oh), ldh,
-                    phf + 4 * (tp * DH + oh) if s < T - 1 else None, ldh,
-                    pdc + 4 * (tn * B * DH + oh) if s else None, DH,
-                    pdc + 4 * (t * B * DH + oh), DH,
-                    pdx + 2 * (t * PW + og), ldp,
-                    pdh + 2 * (t * PW + og), ldp)
-        _bi_steps(fn1, fn2, "hvk_gru_step_bwd", (B, H), dirs, T, step, _s(x))
+            # the step done one launch earlier is at t - k
+            return (pdh + 2 * (ag - k * PW) if s else None, ldp, pwt[d], P,
+                    e, lde, pgt + 2 * ag, ldp, phn + 4 * a, ldh,
+                    phf + 4 * (a + k * DH) if s < T - 1 else None, ldh,
+                    pdc + 4 * (ac - k * BDH) if s else None, DH,
+                    pdc + 4 * ac, DH, pdx + 2 * ag, ldp, pdh + 2 * ag, ldp)
+        _rec_steps(fn1, fn2, "hvk_gru_step_bwd", (B, H), dirs, T, step, _s(x))
         dgx, dgh = dgx_[:, :, :W], dgh_[:, :, :W]
         dgx2 = dgx_.view(B * T, PW)[:, :W]
         dgh2 = dgh_.view(B * T, PW)[:, :W]
@@ -3709,7 +3271,7 @@ def _gru_bwd_dir(err, x, w, save, dw, dbias, accumulate, need_err_input,
                 dc[t][:, hs] = dh * gz
         dgx2, dgh2 = dgx.view(B * T, W), dgh.view(B * T, W)
     save["dgx"], save["dgh"] = dgx, dgh
-    hp = _bi_hprev(save, h_all, dirs, B, T, H).view(B * T, DH)
+    hp = _rec_hprev(save, h_all, dirs, B, T, H).view(B * T, DH)
     sums = None
     if dbias is not None:
         sums = _rec_buf(save, "_dbh", (D, gh), torch.float32, dev)
@@ -3731,13 +3293,8 @@ def _gru_bwd_dir(err, x, w, save, dw, dbias, accumulate, need_err_input,
                 dbias[b0 + gh:b0 + 4 * H] += sums[d, 2 * H:]
             else:
                 dbias[b0 + gh:b0 + 4 * H].copy_(sums[d, 2 * H:])
-    if not need_err_input:
-        return None
-    if err_input is None:
-        err_input = torch.empty(B, T, I, dtype=hdt, device=dev)
-    gemm(dgx2, w[:, :I], out=err_input.view(B * T, I))
-    return err_input
-
+    return _rec_err_input(err_input, dgx2, w, B, T, I, hdt, dev) \
+        if need_err_input else None
 
 # ------------------------------------------- restricted Boltzmann machines
 # docs/OPS.md "Restricted Boltzmann machines"; kernels in csrc/kernels/rbm.hip.
