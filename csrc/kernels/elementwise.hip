@@ -812,11 +812,21 @@ __global__ void space_to_depth_kernel(const uint16_t* __restrict__ x,
 //               same sign -> step*1.2 (<= 50), flip -> step*0.5 (>= 1e-6),
 //               g = 0 ; w -= sign(g)*step ; s2 = g
 // An element outside every segment keeps w, s1 and s2 (see SgdSeg).
+//   4 adam      g with the decay term ; s1 = b1*s1+(1-b1)g ; s2 = b2*s2+(1-b2)g^2
+//               w -= (lr*c1)*s1/(sqrt(s2)*c2+eps)      (moment = b1, rho = b2)
+//   5 adamw     w -= lr*decay*((1-l1)w + l1*sign(w)) ; g WITHOUT the decay
+//               term ; then as adam
+//   6 rmsprop   g with the decay term ; s1 = r*s1+(1-r)g^2 ;
+//               w -= lr*g/(sqrt(s1)+eps)                          (rho = r)
+// c1 = 1/(1-b1^t) and c2 = 1/sqrt(1-b2^t) of the t-th update are rounded to
+// float32 on the host and travel in the table (modes 4 - 6 run only in
+// solver4_kernel / solver1_kernel below).
 struct SolverSeg {
   long long begin, end;
   float lr, decay, l1, moment;
   int mode;
-  float eps, rho, pad;
+  float eps, rho, c1;
+  float c2, pad0, pad1, pad2;
 };
 __global__ void solver_kernel(float* w, float* grad, float* s1, float* s2,
                               uint16_t* w_lp, const SolverSeg* segs, int nseg,
@@ -875,6 +885,221 @@ __global__ void solver_kernel(float* w, float* grad, float* s1, float* s2,
     if (i >= zero_from) grad[i] = 0.f;
     if (w_lp) w_lp[i] = f2bf(wi);
   }
+}
+
+// The seven modes as float4 (solver4_kernel, sgd4_kernel's two paths) and
+// element by element (solver1_kernel: any n, any 4-byte aligned base), with
+// clipping by the global gradient norm:
+//   gscale' = gscale * min(1, clip / (gscale * sqrt(*sqnorm) + 1e-6))
+// read by every thread from device memory (grad_sqnorm below writes it), so a
+// captured step clips by the norm of ITS gradients.  sqnorm == nullptr or
+// clip <= 0: gscale' = gscale exactly.
+__device__ __forceinline__ float clip_scale(float gscale, const float* sqnorm,
+                                            float clip) {
+  if (sqnorm == nullptr || !(clip > 0.f)) return gscale;
+  const float nrm = gscale * sqrtf(*sqnorm);
+  return gscale * fminf(1.f, clip / (nrm + 1e-6f));
+}
+// One element: w, s1 (a) and s2 (b) in place.  Every product-sum is a
+// spelled-out fma and no other expression is contractible, so the float4 and
+// the element path of solver4_kernel and solver1_kernel round alike.
+__device__ __forceinline__ void solver_step(float& wi, float graw, float& a,
+                                            float& b, const SolverSeg& sg,
+                                            float gs) {
+  float g = graw * gs;
+  if (sg.decay != 0.f) {
+    const float sgn = wi > 0.f ? 1.f : (wi < 0.f ? -1.f : 0.f);
+    const float r = __builtin_fmaf(1.f - sg.l1, wi, sg.l1 * sgn);
+    if (sg.mode == 5) wi = __builtin_fmaf(-(sg.lr * sg.decay), r, wi);
+    else g = __builtin_fmaf(sg.decay, r, g);
+  }
+  switch (sg.mode) {
+    case 1: {
+      a = __builtin_fmaf(g, g, a);
+      const float st = (sg.lr * g) / (sqrtf(a) + sg.eps);
+      wi -= st;
+      break;
+    }
+    case 2: {
+      const float omr = 1.f - sg.rho;
+      const float na = __builtin_fmaf(sg.rho, a, (omr * g) * g);
+      const float d = (g * sqrtf(b + sg.eps)) / sqrtf(na + sg.eps);
+      b = __builtin_fmaf(sg.rho, b, (omr * d) * d);
+      a = na;
+      wi = __builtin_fmaf(-sg.lr, d, wi);
+      break;
+    }
+    case 3: {
+      float step = a > 0.f ? a : sg.lr;
+      const float pg = b;
+      // by the signs: the product of two tiny gradients underflows
+      const bool up = (pg > 0.f && g > 0.f) || (pg < 0.f && g < 0.f);
+      const bool down = (pg > 0.f && g < 0.f) || (pg < 0.f && g > 0.f);
+      if (up) step = fminf(step * 1.2f, 50.f);
+      else if (down) { step = fmaxf(step * 0.5f, 1e-6f); g = 0.f; }
+      wi -= (g > 0.f ? step : (g < 0.f ? -step : 0.f));
+      a = step;
+      b = g;
+      break;
+    }
+    case 4:
+    case 5: {
+      a = __builtin_fmaf(sg.moment, a, (1.f - sg.moment) * g);
+      b = __builtin_fmaf(sg.rho, b, ((1.f - sg.rho) * g) * g);
+      const float st = ((sg.lr * sg.c1) * a) /
+                       __builtin_fmaf(sqrtf(b), sg.c2, sg.eps);
+      wi -= st;
+      break;
+    }
+    case 6: {
+      a = __builtin_fmaf(sg.rho, a, ((1.f - sg.rho) * g) * g);
+      const float st = (sg.lr * g) / (sqrtf(a) + sg.eps);
+      wi -= st;
+      break;
+    }
+    default: {
+      a = __builtin_fmaf(sg.moment, a, -(sg.lr * g));
+      wi += a;
+    }
+  }
+}
+__device__ __forceinline__ int seg_search(const SolverSeg* segs, int nseg,
+                                          long long e) {
+  int lo = 0, hi = nseg - 1;
+  while (lo < hi) {
+    int mid = (lo + hi + 1) >> 1;
+    if (segs[mid].begin <= e) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+__global__ void solver4_kernel(float4* w, float4* grad, float4* s1, float4* s2,
+                               uint2* w_lp, const SolverSeg* segs, int nseg,
+                               long long total4, float gscale,
+                               long long zero_from, const float* sqnorm,
+                               float clip) {
+  const float gs = clip_scale(gscale, sqnorm, clip);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total4; i += (long long)gridDim.x * blockDim.x) {
+    const long long e = i * 4;
+    const int lo = seg_search(segs, nseg, e);
+    const SolverSeg sg = segs[lo];
+    float4 wv = w[i], gv = grad[i], av = s1[i];
+    float* wp = (float*)&wv;
+    float* gp = (float*)&gv;
+    float* ap = (float*)&av;
+    if (e >= sg.begin && e + 4 <= sg.end &&
+        (zero_from <= e || zero_from >= e + 4)) {
+      // the whole float4 in one segment and on one side of zero_from; s2 is
+      // touched only by the modes that keep a second state
+      const bool two = sg.mode >= 2 && sg.mode <= 5;
+      float4 bv = two ? s2[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      float* bp = (float*)&bv;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        solver_step(wp[q], gp[q], ap[q], bp[q], sg, gs);
+      w[i] = wv;
+      s1[i] = av;
+      if (two) s2[i] = bv;
+      if (e >= zero_from) grad[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      // a segment end, a gap or zero_from inside the float4: element by
+      // element, each with its own segment; an element outside every
+      // segment is written back with the bits it was read with
+      float4 bv = s2[i];
+      float* bp = (float*)&bv;
+      int k = lo;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const long long eq = e + q;
+        while (k + 1 < nseg && segs[k + 1].begin <= eq) ++k;
+        const SolverSeg sq = segs[k];
+        if (eq >= sq.begin && eq < sq.end)
+          solver_step(wp[q], gp[q], ap[q], bp[q], sq, gs);
+        if (eq >= zero_from) gp[q] = 0.f;
+      }
+      w[i] = wv;
+      s1[i] = av;
+      s2[i] = bv;
+      if (e + 3 >= zero_from) grad[i] = gv;
+    }
+    if (w_lp) {
+      uint2 o;
+      o.x = f2bf(wp[0]) | ((uint32_t)f2bf(wp[1]) << 16);
+      o.y = f2bf(wp[2]) | ((uint32_t)f2bf(wp[3]) << 16);
+      w_lp[i] = o;
+    }
+  }
+}
+// the scalar twin: n % 4 != 0, a base off the 16-B grid, and A/B runs
+// (hvk_set_gemm_variant 67 sends every call here)
+__global__ void solver1_kernel(float* w, float* grad, float* s1, float* s2,
+                               uint16_t* w_lp, const SolverSeg* segs, int nseg,
+                               long long total, float gscale,
+                               long long zero_from, const float* sqnorm,
+                               float clip) {
+  const float gs = clip_scale(gscale, sqnorm, clip);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    const SolverSeg sg = segs[seg_search(segs, nseg, i)];
+    float wi = w[i];
+    if (i >= sg.begin && i < sg.end) {
+      float a = s1[i], b = s2[i];
+      solver_step(wi, grad[i], a, b, sg, gs);
+      w[i] = wi;
+      s1[i] = a;
+      if (sg.mode >= 2 && sg.mode <= 5) s2[i] = b;
+    }
+    if (i >= zero_from) grad[i] = 0.f;
+    if (w_lp) w_lp[i] = f2bf(wi);
+  }
+}
+
+// Sum of squares of a flat float32 buffer in two launches, without atomics
+// and without one workgroup waiting for another, so a rerun gives the same
+// bits: sqnorm_partial_kernel leaves one sum per workgroup in ws (float4
+// loads of the 16-B aligned body, grid-stride; thread 0 of workgroup 0 adds
+// the head before the 16-B grid and the tail first; then the wave, then the
+// four waves through LDS), sqnorm_finish_kernel adds ws[0 .. nws) in one
+// workgroup: thread t takes ws[t], ws[t + 256], ... in index order, then the
+// same wave / LDS tree.
+__device__ __forceinline__ float block_sum256(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ void __launch_bounds__(256)
+sqnorm_partial_kernel(const float* x, long long n, float* ws) {
+  __shared__ float red[4];
+  const long long head =
+      min((long long)(((16 - ((uintptr_t)x & 15)) & 15) >> 2), n);
+  const float4* x4 = (const float4*)(x + head);
+  const long long n4 = (n - head) >> 2;
+  float acc = 0.f;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    for (long long j = 0; j < head; ++j)
+      acc = __builtin_fmaf(x[j], x[j], acc);
+    for (long long j = head + n4 * 4; j < n; ++j)
+      acc = __builtin_fmaf(x[j], x[j], acc);
+  }
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4;
+       i += (long long)gridDim.x * 256) {
+    const float4 v = x4[i];
+    acc = __builtin_fmaf(v.x, v.x, acc);
+    acc = __builtin_fmaf(v.y, v.y, acc);
+    acc = __builtin_fmaf(v.z, v.z, acc);
+    acc = __builtin_fmaf(v.w, v.w, acc);
+  }
+  acc = block_sum256(acc, red);
+  if (threadIdx.x == 0) ws[blockIdx.x] = acc;
+}
+__global__ void __launch_bounds__(256)
+sqnorm_finish_kernel(const float* ws, int nws, float* out) {
+  __shared__ float red[4];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < nws; i += 256) acc += ws[i];
+  acc = block_sum256(acc, red);
+  if (threadIdx.x == 0) out[0] = acc;
 }
 
 
@@ -1532,6 +1757,47 @@ HVK_API int hvk_solver(float* w, float* grad, float* s1, float* s2,
   hipLaunchKernelGGL(solver_kernel, dim3(grid_for(total)), dim3(256), 0, s, w,
                      grad, s1, s2, (uint16_t*)w_lp, (const SolverSeg*)segs,
                      nseg, total, gscale, zero_from);
+  return (int)launch_status(s);
+}
+
+// Every mode of SolverSeg, with optional clipping by the global norm (sqnorm:
+// device pointer to the sum of squares of grad, or null; clip <= 0: off).
+// The float4 kernel when total % 4 == 0 and every base is on its vector grid,
+// the scalar twin otherwise (and always under hvk_set_gemm_variant 67).
+HVK_API int hvk_solver4(float* w, float* grad, float* s1, float* s2,
+                        void* w_lp, const void* segs, int nseg,
+                        long long total, float gscale, long long zero_from,
+                        const float* sqnorm, float clip, hipStream_t s) {
+  if (!w || !grad || !s1 || !s2 || !segs || nseg < 1 || total < 1) return -1;
+  const bool vec = total % 4 == 0 && !((uintptr_t)w & 15) &&
+                   !((uintptr_t)grad & 15) && !((uintptr_t)s1 & 15) &&
+                   !((uintptr_t)s2 & 15) && !((uintptr_t)w_lp & 7) &&
+                   hvk_gemm_variant != 67;
+  if (vec)
+    hipLaunchKernelGGL(solver4_kernel, dim3(grid_for(total / 4)), dim3(256),
+                       0, s, (float4*)w, (float4*)grad, (float4*)s1,
+                       (float4*)s2, (uint2*)w_lp, (const SolverSeg*)segs,
+                       nseg, total / 4, gscale, zero_from, sqnorm, clip);
+  else
+    hipLaunchKernelGGL(solver1_kernel, dim3(grid_for(total)), dim3(256), 0, s,
+                       w, grad, s1, s2, (uint16_t*)w_lp,
+                       (const SolverSeg*)segs, nseg, total, gscale, zero_from,
+                       sqnorm, clip);
+  return (int)launch_status(s);
+}
+
+// out[0] = sum of x[i]^2 over n float32 values (any n >= 1, any 4-byte
+// aligned base); ws holds at least ws_len >= 1 floats of workspace.
+HVK_API int hvk_grad_sqnorm(const float* x, long long n, float* ws,
+                            int ws_len, float* out, hipStream_t s) {
+  if (!x || !ws || !out || n < 1 || ws_len < 1 || ((uintptr_t)x & 3))
+    return -1;
+  int g = grid_for(n / 4);
+  if (g > ws_len) g = ws_len;
+  hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(g), dim3(256), 0, s, x, n,
+                     ws);
+  hipLaunchKernelGGL(sqnorm_finish_kernel, dim3(1), dim3(256), 0, s, ws, g,
+                     out);
   return (int)launch_status(s);
 }
 

@@ -222,6 +222,20 @@ class GradientDescentBase(AcceleratedUnit):
         unknown = self.solvers - set(ops.SOLVERS) - {"fast"}
         if unknown:
             raise ValueError("Unknown solvers %s" % sorted(unknown))
+        # adam / adamw / rmsprop stand alone: none of them combines with
+        # another adaptive rule (the older names keep their precedence)
+        new = self.solvers & set(self.STANDALONE_SOLVERS)
+        if new and len(self.solvers & self.ADAPTIVE_SOLVERS) > 1:
+            raise ValueError(
+                "solver %s cannot be combined with %s" % (
+                    sorted(new)[0], sorted(
+                        (self.solvers & self.ADAPTIVE_SOLVERS) -
+                        {sorted(new)[0]})))
+        self.adam_beta1 = kwargs.get("adam_beta1", 0.9)
+        self.adam_beta2 = kwargs.get("adam_beta2", 0.999)
+        self.adam_epsilon = kwargs.get("adam_epsilon", 1e-8)
+        self.rmsprop_alpha = kwargs.get("rmsprop_alpha", 0.99)
+        self.rmsprop_epsilon = kwargs.get("rmsprop_epsilon", 1e-8)
         self.adagrad_epsilon = kwargs.get("adagrad_epsilon", 1e-8)
         self.adadelta_momentum = kwargs.get("adadelta_momentum", 0.9)
         self.adadelta_epsilon = kwargs.get("adadelta_epsilon", 1e-8)
@@ -257,18 +271,40 @@ class GradientDescentBase(AcceleratedUnit):
                 self.gradient_moment)
 
     SOLVER = None  # a subclass may force one (RPropAll2All: "rprop")
+    STANDALONE_SOLVERS = ("adam", "adamw", "rmsprop")
+    ADAPTIVE_SOLVERS = frozenset(("adagrad", "adadelta", "rprop", "adam",
+                                  "adamw", "rmsprop"))
 
     def solver(self):
-        """(mode, eps, rho) of this unit's update rule (ops.SOLVERS)."""
+        """(mode, eps, rho) of this unit's update rule (ops.SOLVERS); adam
+        and adamw: rho = beta2 (beta1 travels as the segment's moment, see
+        :meth:`solver_moment`), rmsprop: rho = alpha."""
         names = getattr(self, "solvers", ("momentum",))
         if self.SOLVER is not None:
             return ops.SOLVERS[self.SOLVER], 0.0, 0.0
+        for name in ("adam", "adamw"):
+            if name in names:
+                return (ops.SOLVERS[name], getattr(self, "adam_epsilon", 1e-8),
+                        getattr(self, "adam_beta2", 0.999))
+        if "rmsprop" in names:
+            return (ops.SOLVERS["rmsprop"],
+                    getattr(self, "rmsprop_epsilon", 1e-8),
+                    getattr(self, "rmsprop_alpha", 0.99))
         if "adadelta" in names:
             return (ops.SOLVERS["adadelta"], self.adadelta_epsilon,
                     self.adadelta_momentum)
         if "adagrad" in names:
             return ops.SOLVERS["adagrad"], self.adagrad_epsilon, 0.0
         return 0, 0.0, 0.0
+
+    def solver_moment(self, moment):
+        """The ``moment`` field of this unit's segments: beta1 under adam and
+        adamw, nothing under rmsprop (``gradient_moment`` is ignored by the
+        three), ``gradient_moment`` otherwise."""
+        mode = self.solver()[0]
+        if mode in (ops.SOLVERS["adam"], ops.SOLVERS["adamw"]):
+            return getattr(self, "adam_beta1", 0.9)
+        return 0.0 if mode == ops.SOLVERS["rmsprop"] else moment
 
     @property
     def forward(self):
@@ -289,6 +325,15 @@ class GradientDescentBase(AcceleratedUnit):
             mom = arr.mem
             if mom is not None and p is not None and mom.shape == p.shape:
                 p.host_mom = mom
+        # the second solver state and the store's update counters of a
+        # snapshot (steps, and t0: where Adam's bias correction started)
+        for mom2, p in zip(getattr(self, "solver_state2", None) or (),
+                           (fwd._pw_, fwd._pb_)):
+            if mom2 is not None and p is not None and mom2.shape == p.shape:
+                p.host_mom2 = mom2
+        counters = getattr(self, "store_counters", None)
+        if counters is not None:
+            store.steps, store.t0 = counters
 
     def fuse_from(self, producer_unit, act):
         """This unit's err_input will be multiplied by f'(producer.output)
@@ -341,4 +386,14 @@ class GradientDescentBase(AcceleratedUnit):
             if getattr(fwd, "_pb_", None) is not None:
                 self.accumulated_gradient_bias.reset(
                     fwd._pb_.mom.detach().float().cpu().numpy())
+        store = getattr(self, "store_", None)
+        if pw is not None and store is not None and store.finalized:
+            self.store_counters = (store.steps, store.t0)
+            self.solver_state2 = None
+            if store.mom2 is not None:
+                self.solver_state2 = [
+                    None if p is None or p.offset is None else
+                    store.mom2[p.offset:p.offset + p.size].detach().cpu()
+                    .numpy().reshape(p.shape).copy()
+                    for p in (pw, getattr(fwd, "_pb_", None))]
         return super().__getstate__()

@@ -42,7 +42,8 @@ _log = logging.getLogger("params")
 
 class Param(object):
     __slots__ = ("owner", "name", "shape", "host", "offset", "size", "master",
-                 "lp", "grad", "mom", "gd", "is_bias", "bucket", "host_mom")
+                 "lp", "grad", "mom", "gd", "is_bias", "bucket", "host_mom",
+                 "host_mom2")
 
     def __init__(self, owner, name, host):
         self.owner = owner
@@ -56,6 +57,7 @@ class Param(object):
         self.is_bias = name == "bias"
         self.bucket = None
         self.host_mom = None
+        self.host_mom2 = None
 
 
 class ParameterStore(object):
@@ -73,6 +75,18 @@ class ParameterStore(object):
         self._seg_key = None
         self._seg_table = None
         self.steps = 0
+        # ``steps`` when the first Adam segment appeared: the bias correction
+        # of update number steps - t0 + 1 (a net switched to Adam from a
+        # snapshot starts it at 1)
+        self.t0 = None
+        # clipping by the global gradient norm (0: off): every update then
+        # takes the solver path, after one grad_sqnorm over the whole buffer
+        from veles_amd.utils.config import root as _root, get as _get
+        self.clip_norm = float(_get(_root.common.engine.clip_gradient_norm,
+                                    0.0) or 0.0)
+        self._sqnorm = None
+        self._sqnorm_ws = None
+        self._last_gscale = 1.0
         # micro-steps per optimizer step: > 1 after an elastic shrink keeps
         # the global batch (parallel/launch.py ``shrink``)
         from veles_amd.utils.config import root, get
@@ -184,6 +198,11 @@ class ParameterStore(object):
             if p.host_mom is not None and p.host_mom.size == p.size:
                 self.mom[sl].copy_(torch.from_numpy(numpy.ascontiguousarray(
                     p.host_mom, numpy.float32).reshape(-1)))
+            if p.host_mom2 is not None and p.host_mom2.size == p.size:
+                if self.mom2 is None:
+                    self.mom2 = torch.zeros_like(self.mom)
+                self.mom2[sl].copy_(torch.from_numpy(numpy.ascontiguousarray(
+                    p.host_mom2, numpy.float32).reshape(-1)))
         if self.dp is not None and self.dp.world_size > 1:
             self.dp.broadcast_(self.master)
         if self.lp is not None:
@@ -599,9 +618,15 @@ class ParameterStore(object):
         fn = getattr(p.gd, "solver", None)
         return fn() if fn is not None else (0, 0.0, 0.0)
 
+    def _moment_of(self, p, moment):
+        fn = getattr(p.gd, "solver_moment", None)
+        return fn(moment) if fn is not None else moment
+
     def _cached_segments(self):
-        key = tuple((id(p.gd), p.gd.hyper(p.is_bias), self._solver_of(p))
-                    for p in self.params if p.gd is not None)
+        key = tuple((id(p.gd), p.gd.hyper(p.is_bias), self._solver_of(p),
+                     self._moment_of(p, 0.0))
+                    for p in self.params if p.gd is not None) + \
+            (self.clip_norm > 0,)
         if key != self._seg_key:
             self._seg_key = key
             self._segs = self.segments()
@@ -609,12 +634,53 @@ class ParameterStore(object):
             self._segs = _cover(self._segs, self.total)
             solv = {p.offset: self._solver_of(p) for p in self.params
                     if p.gd is not None}
+            beta = {p.offset: p for p in self.params if p.gd is not None}
             self._solver_segs = None
-            if any(m for m, _, _ in solv.values()):
+            if any(m for m, _, _ in solv.values()) or self.clip_norm > 0:
+                # (clipping takes the solver path for every table, all
+                # momentum too: the overlapped updates are off with it)
                 self._solver_segs = [
-                    seg + solv.get(seg[0], (0, 0.0, 0.0))
+                    seg[:5] + (self._moment_of(beta[seg[0]], seg[5])
+                               if seg[0] in beta else seg[5],) +
+                    solv.get(seg[0], (0, 0.0, 0.0))
                     for seg in self._segs]
         return self._segs
+
+    def _update_step(self):
+        """The 1-based number of the coming update for Adam's bias
+        correction (None while no segment is adam / adamw)."""
+        if not any(sg[6] in (4, 5) for sg in self._solver_segs or ()):
+            return None
+        if self.t0 is None:
+            self.t0 = self.steps
+        return self.steps - self.t0 + 1
+
+    def _solver_kwargs(self, gscale):
+        """step / sqnorm / clip_norm of the coming solver update; with
+        clipping on, enqueues the sum of squares of the whole (reduced,
+        accumulated) gradient buffer first."""
+        from veles_amd import ops
+        kw = {"step": self._update_step()}
+        if self.clip_norm > 0:
+            import torch
+            if self._sqnorm is None:
+                self._sqnorm = torch.zeros(1, dtype=torch.float32,
+                                           device=self.grad.device)
+                if self.grad.is_cuda:
+                    self._sqnorm_ws = torch.zeros(
+                        2048, dtype=torch.float32, device=self.grad.device)
+            ops.grad_sqnorm(self.grad, out=self._sqnorm, ws=self._sqnorm_ws)
+            self._last_gscale = gscale
+            kw.update(sqnorm=self._sqnorm, clip_norm=self.clip_norm)
+        return kw
+
+    def last_grad_norm(self):
+        """The norm of the last update's scaled gradient before clipping
+        (``engine.clip_gradient_norm`` > 0; None otherwise).  Synchronises:
+        for logging."""
+        if self._sqnorm is None:
+            return None
+        return self._last_gscale * float(self._sqnorm.cpu()[0]) ** 0.5
 
     def apply(self, gscale=1.0):
         """Wait for the gradient all-reduces, then one fused SGD update."""
@@ -712,11 +778,12 @@ class ParameterStore(object):
             import torch
             if self.mom2 is None:
                 self.mom2 = torch.zeros_like(self.mom)
+            gs = gscale / self.accumulate
             ops.solver_update(self.master, self.grad, self.mom, self.mom2,
-                              self._solver_segs, w_lp=self.lp,
-                              gscale=gscale / self.accumulate,
+                              self._solver_segs, w_lp=self.lp, gscale=gs,
                               zero_grad=self._zero_arg(),
-                              table=self._seg_table)
+                              table=self._seg_table,
+                              **self._solver_kwargs(gs))
         elif segs:
             # the fused kernel also zeroes the gradient buffer (unless every
             # gradient is overwritten next step anyway)
@@ -811,7 +878,10 @@ class ParameterStore(object):
         if self._seg_table is None:
             self._seg_table = ops.SegmentTable(self.master.device)
         if self._solver_segs is not None:
-            self._seg_table.update(ops._pack_solver_segs(self._solver_segs))
+            # Adam's bias correction of the coming update travels in the
+            # table: it changes every step
+            self._seg_table.update(ops._pack_solver_segs(
+                self._solver_segs, step=self._update_step()))
         else:
             self._seg_table.update(ops._pack_sgd_segs(segs))
             # per-bucket tables of the overlapped updates
@@ -835,7 +905,7 @@ class ParameterStore(object):
         """Host-side step state that ``apply`` advances (saved before a HIP
         graph capture pass, restored if that capture fails and the pass is
         re-run eagerly: graphs.py)."""
-        st = {"steps": self.steps, "ready": set(self._ready),
+        st = {"steps": self.steps, "t0": self.t0, "ready": set(self._ready),
               "works": list(self._works), "launched": set(self._launched),
               "accum": self._accum_count, "pending": dict(self._pending),
               "tail_evs": self._tail_evs}
@@ -846,6 +916,7 @@ class ParameterStore(object):
 
     def restore_host_state(self, st):
         self.steps = st["steps"]
+        self.t0 = st.get("t0", self.t0)
         self._ready = set(st["ready"])
         self._works = list(st["works"])
         self._launched = set(st["launched"])
@@ -865,7 +936,8 @@ class ParameterStore(object):
 
     def state_dict(self):
         st = {"master": self.master.detach().cpu(),
-              "mom": self.mom.detach().cpu(), "steps": self.steps}
+              "mom": self.mom.detach().cpu(), "steps": self.steps,
+              "t0": self.t0}
         if self.mom2 is not None:
             st["mom2"] = self.mom2.detach().cpu()
         return st
@@ -880,6 +952,7 @@ class ParameterStore(object):
         if self.lp is not None:
             self.lp.copy_(self.master)
         self.steps = st.get("steps", 0)
+        self.t0 = st.get("t0")
 
 
 class CaptureValidator(object):

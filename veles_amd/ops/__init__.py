@@ -15,6 +15,7 @@ right, bottom), sliding (x, y).
 """
 from __future__ import annotations
 
+import math
 import os
 import struct
 
@@ -1921,11 +1922,33 @@ def _pack_sgd_segs(segs):
                     for b, e, lr, d, l1, m in segs)
 
 
-def _pack_solver_segs(segs):
-    return b"".join(struct.pack(
-        "<qqffffifff", int(b), int(e), float(lr), float(d), float(l1),
-        float(m), int(mode), float(eps), float(rho), 0.0)
-        for b, e, lr, d, l1, m, mode, eps, rho in segs)
+def bias_correction(beta1, beta2, step):
+    """Adam's (c1, c2) = (1 / (1 - b1^t), 1 / sqrt(1 - b2^t)) of the t-th
+    update: the betas as the segment table holds them (float32), the powers
+    in double, the results rounded to float32."""
+    b1, b2, t = _f32(beta1), _f32(beta2), int(step)
+    return (_f32(1.0 / (1.0 - b1 ** t)),
+            _f32(1.0 / math.sqrt(1.0 - b2 ** t)))
+
+
+def _pack_solver_segs(segs, step=None):
+    """SolverSeg rows (csrc/kernels/elementwise.hip) from 9-tuples (begin,
+    end, lr, decay, l1, moment, mode, eps, rho).  Adam rows (modes 4, 5) also
+    carry the bias correction of update number ``step``."""
+    out = []
+    for b, e, lr, d, l1, m, mode, eps, rho in segs:
+        c1 = c2 = 0.0
+        if int(mode) in _ADAM_MODES:
+            if step is None or int(step) < 1:
+                raise ValueError("solver_update: adam / adamw need step >= 1 "
+                                 "(the 1-based update number), not %r" %
+                                 (step,))
+            c1, c2 = bias_correction(m, rho, step)
+        out.append(struct.pack(
+            "<qqffffifffffff", int(b), int(e), float(lr), float(d), float(l1),
+            float(m), int(mode), float(eps), float(rho), c1, c2, 0.0, 0.0,
+            0.0))
+    return b"".join(out)
 
 
 def _segs_tensor(raw, device):
@@ -2048,27 +2071,125 @@ def sgd_update(w, grad, mom, segs, w_lp=None, gscale=1.0, zero_grad=False,
     return w
 
 
-SOLVERS = {"momentum": 0, "adagrad": 1, "adadelta": 2, "rprop": 3}
+SOLVERS = {"momentum": 0, "adagrad": 1, "adadelta": 2, "rprop": 3,
+           "adam": 4, "adamw": 5, "rmsprop": 6}
+_ADAM_MODES = (4, 5)
+
+_SQNORM_WS = {}
+_SQNORM_WS_LEN = 2048      # one partial sum per workgroup of the first launch
+_SQNORM_CHUNK = 4096       # CPU path: float32 sums of chunks, then of those
+
+
+def grad_sqnorm(grad, out=None, ws=None):
+    """Sum of squares of a flat float32 buffer into ``out`` (1-element
+    float32 tensor on grad's device, allocated if None).  GPU: two launches,
+    no atomics, bit-identical from run to run (``sqnorm_partial_kernel`` /
+    ``sqnorm_finish_kernel``); ``ws``: float32 workspace of up to 2048
+    elements (a per-device one is kept otherwise).  CPU: a float32 sum."""
+    n = grad.numel()
+    if n < 1 or grad.dtype != torch.float32 or not grad.is_contiguous():
+        raise ValueError("grad_sqnorm needs a contiguous float32 buffer of "
+                         "n >= 1 elements")
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=grad.device)
+    if _gpu(grad):
+        if ws is None:
+            ws = _SQNORM_WS.get(grad.device)
+            if ws is None:
+                ws = _SQNORM_WS[grad.device] = torch.empty(
+                    _SQNORM_WS_LEN, dtype=torch.float32, device=grad.device)
+        _lib_call("hvk_grad_sqnorm", _p(grad), n, _p(ws), ws.numel(),
+                  _p(out), _s(grad))
+        return out
+    sq = grad.reshape(-1) * grad.reshape(-1)
+    k = n // _SQNORM_CHUNK * _SQNORM_CHUNK
+    parts = sq[:k].view(-1, _SQNORM_CHUNK).sum(1)
+    out[0] = torch.cat([parts, sq[k:].sum().reshape(1)]).sum()
+    return out
+
+
+def clip_scale(gscale, sqnorm, clip_norm):
+    """gscale' = gscale * min(1, clip / (gscale * sqrt(sqnorm) + 1e-6)) in
+    float32 operations, as every thread of the update kernel computes it
+    (the rule of ``torch.nn.utils.clip_grad_norm_`` on the scaled gradient).
+    ``sqnorm`` None or ``clip_norm`` <= 0: ``gscale`` (as float32)."""
+    import numpy as np
+    gs = np.float32(gscale)
+    if sqnorm is None or not clip_norm > 0:
+        return float(gs)
+    with np.errstate(all="ignore"):
+        nrm = gs * np.sqrt(np.float32(float(sqnorm.reshape(-1)[0])))
+        coef = np.fmin(np.float32(1.0),
+                       np.float32(clip_norm) / (nrm + np.float32(1e-6)))
+        return float(gs * coef)
+
+
+def _adam_cpu(ws, g, a, c, lr, d, l1, m, mode, eps, rho, c1, c2):
+    """Modes 4 - 6 on float32 CPU views, scalar by scalar as the kernel's
+    ``solver_step`` (which fuses some of the product-sums)."""
+    import numpy as np
+    f = np.float32
+    one = f(1.0)
+    if d:
+        r = float(one - f(l1)) * ws + float(f(l1)) * torch.sign(ws)
+        if mode == 5:
+            ws -= float(f(lr) * f(d)) * r
+        else:
+            g = g + float(f(d)) * r
+    if mode == 6:
+        a.mul_(float(f(rho))).add_(float(one - f(rho)) * g * g)
+        ws -= float(f(lr)) * g / (a.sqrt() + float(f(eps)))
+        return
+    a.mul_(float(f(m))).add_(float(one - f(m)) * g)
+    c.mul_(float(f(rho))).add_(float(one - f(rho)) * g * g)
+    ws -= float(f(lr) * f(c1)) * a / (c.sqrt() * c2 + float(f(eps)))
 
 
 def solver_update(w, grad, s1, s2, segs, w_lp=None, gscale=1.0,
-                  zero_grad=False, table=None):
+                  zero_grad=False, table=None, step=None, sqnorm=None,
+                  clip_norm=0.0):
     """Fused multi-segment update with a solver per segment.
 
     segs: [(begin, end, lr, decay, l1_vs_l2, moment, mode, eps, rho)], modes
-    in :data:`SOLVERS` (csrc/kernels/elementwise.hip ``solver_kernel``)."""
+    in :data:`SOLVERS`.  adam / adamw: moment = beta1, rho = beta2 and
+    ``step`` (>= 1) is the update number of the bias correction, which
+    travels in the table; rmsprop: rho = alpha.  ``sqnorm`` (1-element
+    float32 tensor, see :func:`grad_sqnorm`) with ``clip_norm`` > 0 clips
+    the scaled gradient by its global norm (:func:`clip_scale`).  Tables of
+    modes 0 - 3 without clipping run ``solver_kernel``, everything else
+    ``solver4_kernel`` or its scalar twin (csrc/kernels/elementwise.hip)."""
     n = w.numel()
     zf = _zero_from(zero_grad, n)
+    clip = float(clip_norm) if sqnorm is not None and clip_norm and \
+        clip_norm > 0 else 0.0
+    new = clip > 0 or any(int(sg[6]) >= 4 for sg in segs)
+    if any(int(sg[6]) in _ADAM_MODES for sg in segs) and \
+            (step is None or int(step) < 1):
+        raise ValueError("solver_update: adam / adamw need step >= 1 (the "
+                         "1-based update number), not %r" % (step,))
     if _gpu(w):
-        raw = _pack_solver_segs(segs)
+        raw = _pack_solver_segs(segs, step)
         st = table.update(raw) if table is not None else \
             _segs_tensor(raw, w.device)
-        _lib_call("hvk_solver", _p(w), _p(grad), _p(s1), _p(s2), _p(w_lp),
-                  _p(st), len(segs), n, float(gscale), zf, _s(w))
+        if new:
+            _lib_call("hvk_solver4", _p(w), _p(grad), _p(s1), _p(s2),
+                      _p(w_lp), _p(st), len(segs), n, float(gscale), zf,
+                      _p(sqnorm) if clip > 0 else None, clip, _s(w))
+        else:
+            _lib_call("hvk_solver", _p(w), _p(grad), _p(s1), _p(s2),
+                      _p(w_lp), _p(st), len(segs), n, float(gscale), zf,
+                      _s(w))
         return w
+    if clip > 0:
+        gscale = clip_scale(gscale, sqnorm, clip)
     for b, e, lr, d, l1, m, mode, eps, rho in segs:
         ws = w[b:e]
         g = grad[b:e] * gscale
+        if mode >= 4:
+            c1, c2 = bias_correction(m, rho, step) if mode != 6 else (0., 0.)
+            _adam_cpu(ws, g, s1[b:e], s2[b:e], lr, d, l1, m, mode, eps, rho,
+                      c1, c2)
+            continue
         if d:
             g = g + d * ((1 - l1) * ws + l1 * torch.sign(ws))
         a = s1[b:e]

@@ -167,6 +167,11 @@ _OPTIONAL = {
     "hvk_rbm_sample": [I, I, I, I, P, L, P, L, P, P, L, P, L, U, P, L, P],
     "hvk_rbm_grad_splits": [I, I, I, I],
     "hvk_rbm_grad": [I, I, I] + [P, L] * 4 + [P, F, P, I, P],
+    # adam / adamw / rmsprop and clipping by the global gradient norm
+    # (csrc/kernels/elementwise.hip): (w, grad, s1, s2, w_lp, segs, nseg,
+    # total, gscale, zero_from, sqnorm, clip, s) and (x, n, ws, ws_len, out, s)
+    "hvk_solver4": [P, P, P, P, P, P, I, L, F, L, P, F, P],
+    "hvk_grad_sqnorm": [P, L, P, I, P, P],
 }
 # functions returning a pointer / a 64-bit int (every other one returns int)
 _PTR_RET = {"hvk_stream_create"}
