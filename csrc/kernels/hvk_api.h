@@ -27,6 +27,25 @@ int hvk_pool_fwd(const void* x, void* y, int* argmax, int N, int H, int W,
                  int pl, int mode, hipStream_t s);
 int hvk_lrn_fwd(const void* x, void* y, long long P, int C, int n, float alpha,
                 float beta, float k, hipStream_t s);
+// batch normalisation (batchnorm.hip): table [2][C] = scale, shift
+int hvk_bn_partials(long long P, int C, int vec);
+int hvk_bn_vec(const void* x, long long ldx, int C);
+int hvk_bn_stats(const void* x, long long ldx, long long P, int C, int vec,
+                 const float* gamma, const float* beta, float* running_mean,
+                 float* running_var, float eps, float momentum, float* mean,
+                 float* invstd, float* table, float* ws, hipStream_t s);
+int hvk_bn_fold(const float* gamma, const float* beta,
+                const float* running_mean, const float* running_var, int C,
+                float eps, float* table, hipStream_t s);
+int hvk_bn_apply(const void* x, long long ldx, void* y, long long ldy,
+                 long long P, int C, const float* table, int act,
+                 hipStream_t s);
+int hvk_bn_bwd(const void* x, long long ldx, const void* err, long long lde,
+               const void* y, long long ldy, const void* aux, long long lda,
+               void* dx, long long lddx, long long P, int C, int vec,
+               const float* gamma, const float* mean, const float* invstd,
+               float* dgamma, float* dbeta, int accumulate, int act,
+               int aux_act, float* coef, float* ws, hipStream_t s);
 int hvk_act_fwd(const void* x, int xdt, void* y, int ydt, long long n, int act,
                 hipStream_t s);
 int hvk_softmax_ce(const void* logits, int in_dt, int B, int C,

@@ -362,6 +362,65 @@ class LRN : public Unit {
   int n_ = 5;
 };
 
+// y = act(x * scale_c + shift_c) over the last axis, scale and shift folded
+// once from gamma, beta and the running statistics of the package
+class BatchNorm : public Unit {
+ public:
+  using Unit::Unit;
+  ~BatchNorm() override {
+    if (dtable_) (void)hipFree(dtable_);
+  }
+  std::string Class() const override { return "BatchNorm"; }
+  void SetParameter(const std::string& k, const Json& v,
+                    const std::map<std::string, NpyArray>& a) override {
+    if (k == "weights") gamma_ = Arr(v, a);
+    else if (k == "bias") beta_ = Arr(v, a);
+    else if (k == "running_mean") mean_ = Arr(v, a);
+    else if (k == "running_var") var_ = Arr(v, a);
+    else if (k == "eps") eps_ = (float)v.num;
+    else if (k == "activation_mode") act_ = ActCode(v.str);
+  }
+  Shape OutputShape(const Shape& in) const override { return in; }
+  void Initialize(ExecContext& ctx) override {
+    const size_t C = gamma_.data.size();
+    if (!C || beta_.data.size() != C || mean_.data.size() != C ||
+        var_.data.size() != C)
+      throw std::runtime_error(name_ + ": gamma, beta and the running "
+                               "statistics must have one length");
+    if (table_.empty()) {
+      table_.resize(2 * C);
+      for (size_t c = 0; c < C; ++c) {
+        const float sc = gamma_.data[c] / std::sqrt(var_.data[c] + eps_);
+        table_[c] = sc;
+        table_[C + c] = beta_.data[c] - mean_.data[c] * sc;
+      }
+    }
+    if (ctx.gpu && !dtable_) dtable_ = UploadF32(table_);
+  }
+  void Execute(const Tensor& in, Tensor& out, ExecContext& ctx) override {
+    const size_t C = in.shape.back(), P = numel(in.shape) / C;
+    if (C * 2 != table_.size()) throw std::runtime_error(name_ + ": input");
+    if (ctx.gpu) {
+      HVKCHECK(hvk_bn_apply(in.data, (long long)C, out.data, (long long)C,
+                            (long long)P, (int)C, (const float*)dtable_, act_,
+                            ctx.stream));
+      return;
+    }
+    const float* x = (const float*)in.data;
+    float* y = (float*)out.data;
+    for (size_t p = 0; p < P; ++p)
+      for (size_t c = 0; c < C; ++c)
+        y[p * C + c] = Act(x[p * C + c] * table_[c] + table_[C + c], act_);
+  }
+
+ private:
+  NpyArray gamma_, beta_, mean_, var_;
+  std::vector<float> table_;
+  float eps_ = 1e-5f;
+  int act_ = 0;
+  void* dtable_ = nullptr;
+};
+
 class Identity : public Unit {
  public:
   using Unit::Unit;
@@ -420,6 +479,11 @@ VELES_REGISTER_UNIT(MaxPooling, "MaxPooling");
 VELES_REGISTER_UNIT(AvgPooling, "AvgPooling");
 VELES_REGISTER_UNIT(MaxAbsPooling, "MaxAbsPooling");
 VELES_REGISTER_UNIT(LRN, "LRNormalizerForward");
+VELES_REGISTER_UNIT(BatchNorm, "BatchNorm");
+VELES_REGISTER_UNIT(BatchNorm, "BatchNormTanh");
+VELES_REGISTER_UNIT(BatchNorm, "BatchNormRELU");
+VELES_REGISTER_UNIT(BatchNorm, "BatchNormStrictRELU");
+VELES_REGISTER_UNIT(BatchNorm, "BatchNormSigmoid");
 VELES_REGISTER_UNIT(Identity, "DropoutForward");
 VELES_REGISTER_UNIT(ActN<1>, "ForwardTanh");
 VELES_REGISTER_UNIT(ActN<2>, "ForwardRELU");

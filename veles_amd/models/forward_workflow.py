@@ -80,6 +80,13 @@ class ForwardWorkflow(StandardWorkflow):
                 if getattr(src, "include_bias", False) and \
                         src.bias.mem is not None:
                     dst.bias.reset(src.bias.mem.copy())
+            if hasattr(src, "sync_running_to_host") and \
+                    src.running_mean.mem is not None:
+                # batch normalisation: the running statistics are trained
+                # state too
+                src.sync_running_to_host()
+                dst.running_mean.reset(src.running_mean.mem.copy())
+                dst.running_var.reset(src.running_var.mem.copy())
         fwd.loader.derive_from(trained.loader)
         return fwd
 

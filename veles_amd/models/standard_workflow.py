@@ -25,6 +25,7 @@ import re
 from veles_amd.accelerated_units import AcceleratedWorkflow
 from veles_amd.loader.base import UserLoaderRegistry
 from veles_amd.models import activation as act_units
+from veles_amd.models import batch_norm as bn_units
 from veles_amd.models.all2all import (
     All2All, All2AllRELU, All2AllSigmoid, All2AllSoftmax, All2AllStrictRELU,
     All2AllTanh, ResizableAll2All)
@@ -93,6 +94,13 @@ LAYER_TYPES = {
     "rnn": (RNN, GDRNN),
     "gru": (GRU, GDGRU),
     "norm": (LRNormalizerForward, LRNormalizerBackward),
+    "batch_norm": (bn_units.BatchNorm, bn_units.GDBatchNorm),
+    "batch_norm_tanh": (bn_units.BatchNormTanh, bn_units.GDBatchNormTanh),
+    "batch_norm_relu": (bn_units.BatchNormRELU, bn_units.GDBatchNormRELU),
+    "batch_norm_str": (bn_units.BatchNormStrictRELU,
+                       bn_units.GDBatchNormStrictRELU),
+    "batch_norm_sigmoid": (bn_units.BatchNormSigmoid,
+                           bn_units.GDBatchNormSigmoid),
     "dropout": (DropoutForward, DropoutBackward),
     "activation_tanh": (act_units.ForwardTanh, act_units.BackwardTanh),
     "activation_relu": (act_units.ForwardRELU, act_units.BackwardRELU),
@@ -110,7 +118,7 @@ LAYER_TYPES = {
 # GD classes whose err_input kernel can multiply by f'(aux) in its epilogue
 _FUSABLE = (GradientDescent, GradientDescentConv, GDMaxPooling, GDAvgPooling,
             GDMaxAbsPooling, LRNormalizerBackward, DropoutBackward,
-            act_units.ActivationBackward)
+            act_units.ActivationBackward, bn_units.GDBatchNorm)
 _POOL_KW = ("kx", "ky", "sliding")
 _LRN_KW = ("alpha", "beta", "k", "n")
 
@@ -289,7 +297,7 @@ class StandardWorkflow(LinkBuilders, AcceleratedWorkflow):
             else:
                 unit.link_from(prev)
                 unit.link_attrs(prev, ("input", "output"))
-            if isinstance(unit, DropoutForward):
+            if isinstance(unit, (DropoutForward, bn_units.BatchNorm)):
                 unit.link_attrs(self.loader, "minibatch_class")
             # encoder/decoder pairing (auto-encoders): depooling inverts the
             # latest pooling, deconv the latest conv (LIFO)

@@ -5,13 +5,15 @@ conventional definitions, written as StandardWorkflow ``layers`` lists.
 * mnist_fc   : 784 -> all2all_tanh(100) -> softmax(10)   (export fixture)
 * lenet      : Caffe LeNet (conv 20x5x5, pool, conv 50x5x5, pool, 500, 10)
 * cifar_quick: Caffe cifar10_quick (3x conv 5x5 32/32/64 + pools, 64, 10)
+* cifar_quick_bn: the same convolutions, each followed by a batch
+  normalisation with the strict ReLU in it
 * alexnet    : Caffe bvlc_alexnet, 227x227x3, grouped conv2/4/5, LRN
 * vgg16      : VGG-16 (13 conv 3x3 + 5 pools, 4096-4096-1000)
 """
 from __future__ import annotations
 
-__all__ = ["mnist_fc", "lenet", "cifar_quick", "alexnet", "vgg16", "MODELS",
-           "gd_params"]
+__all__ = ["mnist_fc", "lenet", "cifar_quick", "cifar_quick_bn", "alexnet",
+           "vgg16", "MODELS", "gd_params"]
 
 
 def gd_params(lr=0.01, moment=0.9, decay=5e-4, lr_bias=None):
@@ -59,6 +61,29 @@ def cifar_quick(lr=0.001):
                                    "weights_stddev": 0.1}, "<-": g},
         {"type": "softmax", "->": {"output_sample_shape": 10,
                                    "weights_stddev": 0.1}, "<-": g}]
+
+
+def cifar_quick_bn(lr=0.01):
+    """cifar_quick with conv -> ``batch_norm_str`` blocks: the convolutions
+    are linear and carry no bias (the normalisation removes it), gamma and
+    beta take no weight decay."""
+    g = gd_params(lr, 0.9, 4e-3)
+    bn = dict(gd_params(lr, 0.9, 0.0, lr))
+    pool = {"kx": 3, "ky": 3, "sliding": 2}
+
+    def block(n, stddev):
+        return [{"type": "conv", "->": {"n_kernels": n, "kx": 5, "ky": 5,
+                                        "padding": 2, "include_bias": False,
+                                        "weights_stddev": stddev},
+                 "<-": dict(g)},
+                {"type": "batch_norm_str", "<-": dict(bn)}]
+    return (block(32, 0.01) + [{"type": "max_pooling", "->": dict(pool)}] +
+            block(32, 0.01) + [{"type": "avg_pooling", "->": dict(pool)}] +
+            block(64, 0.01) + [{"type": "avg_pooling", "->": dict(pool)}] + [
+        {"type": "all2all", "->": {"output_sample_shape": 64,
+                                   "weights_stddev": 0.1}, "<-": dict(g)},
+        {"type": "softmax", "->": {"output_sample_shape": 10,
+                                   "weights_stddev": 0.1}, "<-": dict(g)}])
 
 
 def alexnet(lr=0.01, n_classes=1000):

@@ -32,7 +32,8 @@ __all__ = ["ACT", "gemm", "linear_fwd", "conv_out_size", "conv_fwd",
            "xorshift128plus", "join", "cast", "fill_minibatch",
            "mean_disp_normalize", "act_code", "kohonen_coords",
            "kohonen_argmin", "kohonen_update", "lstm_fwd", "lstm_bwd",
-           "rbm_layout", "rbm_uniforms", "rbm_sample", "rbm_grad"]
+           "rbm_layout", "rbm_uniforms", "rbm_sample", "rbm_grad",
+           "bn_partials", "batchnorm_fwd", "batchnorm_bwd"]
 
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2, torch.int32: 3,
       torch.float16: 4}
@@ -1735,6 +1736,264 @@ def lrn_bwd(x, dy, n=5, alpha=1e-4, beta=0.75, k=2.0, aux=None, aux_act=0,
     if aux is not None:
         dx = dx * act_bwd_ref(aux.float(), aux_act)
     out.copy_(dx.to(out.dtype))
+    return out
+
+
+# ------------------------------------------------------ batch normalisation
+BN_CPU_CHAIN = 64     # CPU path: float32 sums of 64 rows, then of those
+
+
+def _bn_fn(name):
+    fn = getattr(_lib.lib(), name, None)
+    if fn is None:
+        raise _lib.KernelLibraryMissing(
+            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
+            (_lib.LIB_PATH, name))
+    return fn
+
+
+def bn_partials(P, C, vec):
+    """Partials per channel of the two-launch reductions of ``hvk_bn_stats``
+    and ``hvk_bn_bwd`` over [P][C]: a function of the shape and the path
+    (``vec``: 8 channels per lane) only, never of the device."""
+    g = _bn_fn("hvk_bn_partials")(int(P), int(C), int(bool(vec)))
+    if g < 1:
+        raise ValueError("batchnorm: no grid for P = %d, C = %d, vec = %s" %
+                         (P, C, vec))
+    return g
+
+
+def _bn_chain_sum(t):
+    """[P][C] float32 -> [C]: chains of BN_CPU_CHAIN rows, then their sums
+    (no float32 chain is longer than BN_CPU_CHAIN + P / BN_CPU_CHAIN + 1)"""
+    P = t.shape[0]
+    k = P // BN_CPU_CHAIN * BN_CPU_CHAIN
+    parts = [t[:k].view(-1, BN_CPU_CHAIN, t.shape[1]).sum(1)] if k else []
+    if k < P:
+        parts.append(t[k:].sum(0, keepdim=True))
+    return torch.cat(parts).sum(0)
+
+
+def _bn_rows(name, what, t, like=None):
+    """(P, C, pitch) of a tensor whose last axis is the channel axis: any
+    contiguous shape, or a 2-D view with contiguous rows"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: %s must be a tensor, got %s" % (
+            name, what, type(t).__name__))
+    if t.dim() < 1 or t.numel() < 1:
+        raise ValueError("%s: %s is empty" % (name, what))
+    C = t.shape[-1]
+    if t.is_contiguous():
+        ld = C
+    elif t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= C:
+        ld = t.stride(0)
+    else:
+        raise ValueError("%s: %s must be contiguous, or 2-D with contiguous "
+                         "rows (strides %s)" % (name, what, t.stride()))
+    if t.numel() >= 1 << 31:
+        raise ValueError("%s: %s has %d elements, the limit is 2^31 - 1" % (
+            name, what, t.numel()))
+    if like is not None:
+        if tuple(t.shape) != tuple(like.shape):
+            raise ValueError("%s: %s is %s, x is %s" % (
+                name, what, tuple(t.shape), tuple(like.shape)))
+        if t.dtype != like.dtype:
+            raise TypeError("%s: %s is %s, x is %s" % (
+                name, what, t.dtype, like.dtype))
+        if t.device != like.device:
+            raise ValueError("%s: %s is on %s, x on %s" % (
+                name, what, t.device, like.device))
+    return t.numel() // C, C, ld
+
+
+def _bn_vecs(name, C, x, **vecs):
+    for what, v in vecs.items():
+        if not isinstance(v, torch.Tensor):
+            raise TypeError("%s: %s must be a tensor, got %s" % (
+                name, what, type(v).__name__))
+        if v.dtype != torch.float32:
+            raise TypeError("%s: %s must be float32, not %s" % (
+                name, what, v.dtype))
+        if tuple(v.shape) != (C,) or not v.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous [%d], got %s" % (
+                name, what, C, tuple(v.shape)))
+        if v.device != x.device:
+            raise ValueError("%s: %s is on %s, x on %s" % (
+                name, what, v.device, x.device))
+
+
+def _bn_xdtype(name, x):
+    want = torch.bfloat16 if _gpu(x) else torch.float32
+    if x.dtype != want:
+        raise TypeError("%s: x must be %s on %s, not %s" % (
+            name, want, x.device.type, x.dtype))
+
+
+def _bn_vec(C, *pairs):
+    fn = _bn_fn("hvk_bn_vec")
+    return C % 8 == 0 and all(
+        t is None or fn(_p(t), int(ld), C) for t, ld in pairs)
+
+
+def batchnorm_fwd(x, gamma, beta, running_mean, running_var, training=True,
+                  eps=1e-5, momentum=0.1, act=0, save=None, out=None,
+                  ws=None):
+    """Batch normalisation over the last axis of ``x`` (every other axis is
+    a row): ``torch.nn.BatchNorm2d`` / ``BatchNorm1d`` followed by one of
+    this project's activations.
+
+    ``training``: y = act(gamma (x - mean) invstd + beta) with the rows'
+    mean and biased variance; ``running_mean`` / ``running_var`` move by
+    ``momentum`` towards the mean and the unbiased variance; ``save`` gets
+    ``mean``, ``invstd`` (float32 [C]) and ``table`` (float32 [2][C]: scale
+    = gamma invstd, shift = beta - mean scale).  Otherwise the running
+    statistics take the place of the rows' and stay as they are.
+
+    GPU: bf16 ``x`` / ``out``, float32 everything else (``hvk_bn_stats`` or
+    ``hvk_bn_fold``, then ``hvk_bn_apply``).  CPU: float32 throughout.  A
+    caller that keeps ``save`` and ``ws`` (dicts) gets the same buffers at
+    every call."""
+    name = "batchnorm_fwd"
+    P, C, ldx = _bn_rows(name, "x", x)
+    _bn_xdtype(name, x)
+    _bn_vecs(name, C, x, gamma=gamma, beta=beta, running_mean=running_mean,
+             running_var=running_var)
+    act = act_code(act)
+    if not 0 <= act <= 4:
+        raise ValueError("%s: unknown activation %r" % (name, act))
+    if training and P < 2:
+        raise ValueError("%s: training needs more than one value per "
+                         "channel, got %d" % (name, P))
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    _, _, ldy = _bn_rows(name, "out", out, like=x)
+    save = {} if save is None else save
+    ws = {} if ws is None else ws
+    dev = x.device
+    mean = _rec_buf(save, "mean", (C,), torch.float32, dev)
+    invstd = _rec_buf(save, "invstd", (C,), torch.float32, dev)
+    table = _rec_buf(save, "table", (2, C), torch.float32, dev)
+    if _gpu(x):
+        s = _s(x)
+        if training:
+            vec = _bn_vec(C, (x, ldx))
+            G = bn_partials(P, C, vec)
+            w = _rec_buf(ws, "stats", (2 * C * G,), torch.float32, dev)
+            _lib.check(_bn_fn("hvk_bn_stats")(
+                _p(x), ldx, P, C, int(vec), _p(gamma), _p(beta),
+                _p(running_mean), _p(running_var), float(eps),
+                float(momentum), _p(mean), _p(invstd), _p(table), _p(w), s),
+                "hvk_bn_stats")
+        else:
+            _lib.check(_bn_fn("hvk_bn_fold")(
+                _p(gamma), _p(beta), _p(running_mean), _p(running_var), C,
+                float(eps), _p(table), s), "hvk_bn_fold")
+        _lib.check(_bn_fn("hvk_bn_apply")(
+            _p(x), ldx, _p(out), ldy, P, C, _p(table), act, s),
+            "hvk_bn_apply")
+        return out
+    x2 = x.reshape(P, C)
+    if training:
+        m = _bn_chain_sum(x2) / P
+        d = x2 - m
+        var = _bn_chain_sum(d * d) / P
+        mean.copy_(m)
+        invstd.copy_(1.0 / torch.sqrt(var + eps))
+        running_mean.mul_(1.0 - momentum).add_(momentum * m)
+        running_var.mul_(1.0 - momentum).add_(
+            momentum * (var * (P / (P - 1.0))))
+        table[0].copy_(gamma * invstd)
+        table[1].copy_(beta - m * table[0])
+        y = d * table[0] + beta
+    else:
+        table[0].copy_(gamma / torch.sqrt(running_var + eps))
+        table[1].copy_(beta - running_mean * table[0])
+        y = (x2 - running_mean) * table[0] + beta
+    out.copy_(act_fwd_ref(y, act).view(out.shape))
+    return out
+
+
+def batchnorm_bwd(err, x, y, gamma, save, dgamma, dbeta, act=0,
+                  accumulate="overwrite", aux=None, aux_act=0, out=None,
+                  ws=None, need_dx=True):
+    """Backward of ``batchnorm_fwd(training=True)``.  g = err f'(y) when
+    ``act`` is this layer's activation (0: ``y`` is not read and may be
+    None); dbeta = sum g, dgamma = sum g xhat, written (``"overwrite"``) or
+    added (True) to ``dbeta`` / ``dgamma``; returns dx = gamma invstd (g -
+    dbeta / P - xhat dgamma / P), times f'(aux) of the layer below when
+    ``aux_act`` is set (None with ``need_dx`` False).  ``save`` is the
+    forward's.  GPU: ``hvk_bn_bwd`` (two reduction launches and the dx
+    pass); CPU: float32."""
+    name = "batchnorm_bwd"
+    P, C, ldx = _bn_rows(name, "x", x)
+    _bn_xdtype(name, x)
+    _, _, lde = _bn_rows(name, "err", err, like=x)
+    act, aux_act = act_code(act), act_code(aux_act)
+    if not 0 <= act <= 4 or not 0 <= aux_act <= 4:
+        raise ValueError("%s: unknown activation %r / %r" % (
+            name, act, aux_act))
+    if accumulate not in (True, "overwrite"):
+        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
+                         name)
+    ldy = lda = lddx = C
+    if act:
+        if y is None:
+            raise ValueError("%s: the activation's derivative needs y" % name)
+        _, _, ldy = _bn_rows(name, "y", y, like=x)
+    else:
+        y = None
+    if aux_act:
+        if aux is None:
+            raise ValueError("%s: aux_act without aux" % name)
+        _, _, lda = _bn_rows(name, "aux", aux, like=x)
+    else:
+        aux = None
+    _bn_vecs(name, C, x, gamma=gamma, dgamma=dgamma, dbeta=dbeta)
+    dev = x.device
+    _rec_save_check(name, "batchnorm_fwd", save,
+                    (("mean", (C,), torch.float32),
+                     ("invstd", (C,), torch.float32)), dev)
+    if P < 2:
+        raise ValueError("%s: training needs more than one value per "
+                         "channel, got %d" % (name, P))
+    if need_dx:
+        if out is None:
+            out = torch.empty(x.shape, dtype=x.dtype, device=dev)
+        _, _, lddx = _bn_rows(name, "out", out, like=x)
+    else:
+        out = None
+    ws = {} if ws is None else ws
+    mean, invstd = save["mean"], save["invstd"]
+    if _gpu(x):
+        vec = _bn_vec(C, (x, ldx), (err, lde), (y, ldy), (aux, lda),
+                      (out, lddx))
+        G = bn_partials(P, C, vec)
+        w = _rec_buf(ws, "bwd", (2 * C * G,), torch.float32, dev)
+        coef = _rec_buf(ws, "coef", (3, C), torch.float32, dev)
+        _lib.check(_bn_fn("hvk_bn_bwd")(
+            _p(x), ldx, _p(err), lde, _p(y), ldy, _p(aux), lda, _p(out),
+            lddx, P, C, int(vec), _p(gamma), _p(mean), _p(invstd),
+            _p(dgamma), _p(dbeta), int(accumulate is True), act, aux_act,
+            _p(coef), _p(w), _s(x)), "hvk_bn_bwd")
+        return out
+    g = err.reshape(P, C)
+    if act:
+        g = g * act_bwd_ref(y.reshape(P, C), act)
+    xh = (x.reshape(P, C) - mean) * invstd
+    db = _bn_chain_sum(g)
+    dg = _bn_chain_sum(g * xh)
+    if accumulate is True:
+        dbeta.add_(db)
+        dgamma.add_(dg)
+    else:
+        dbeta.copy_(db)
+        dgamma.copy_(dg)
+    if out is None:
+        return None
+    dx = (gamma * invstd) * (g - db / P - xh * (dg / P))
+    if aux_act:
+        dx = dx * act_bwd_ref(aux.reshape(P, C), aux_act)
+    out.copy_(dx.view(out.shape))
     return out
 
 

@@ -172,6 +172,18 @@ _OPTIONAL = {
     # total, gscale, zero_from, sqnorm, clip, s) and (x, n, ws, ws_len, out, s)
     "hvk_solver4": [P, P, P, P, P, P, I, L, F, L, P, F, P],
     "hvk_grad_sqnorm": [P, L, P, I, P, P],
+    # batch normalisation (csrc/kernels/batchnorm.hip): (P, C, vec); (x, ldx,
+    # C); (x, ldx, P, C, vec, gamma, beta, running_mean, running_var, eps,
+    # momentum, mean, invstd, table, ws, s); (gamma, beta, running_mean,
+    # running_var, C, eps, table, s); (x, ldx, y, ldy, P, C, table, act, s);
+    # (x, err, y, aux, dx each with its pitch, P, C, vec, gamma, mean, invstd,
+    # dgamma, dbeta, accumulate, act, aux_act, coef, ws, s)
+    "hvk_bn_partials": [L, I, I],
+    "hvk_bn_vec": [P, L, I],
+    "hvk_bn_stats": [P, L, L, I, I, P, P, P, P, F, F, P, P, P, P, P],
+    "hvk_bn_fold": [P, P, P, P, I, F, P, P],
+    "hvk_bn_apply": [P, L, P, L, L, I, P, I, P],
+    "hvk_bn_bwd": [P, L] * 5 + [L, I, I, P, P, P, P, P, I, I, I, P, P, P],
 }
 # functions returning a pointer / a 64-bit int (every other one returns int)
 _PTR_RET = {"hvk_stream_create"}
