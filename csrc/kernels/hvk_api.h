@@ -46,6 +46,27 @@ int hvk_bn_bwd(const void* x, long long ldx, const void* err, long long lde,
                const float* gamma, const float* mean, const float* invstd,
                float* dgamma, float* dbeta, int accumulate, int act,
                int aux_act, float* coef, float* ws, hipStream_t s);
+// self-attention (attention.hip): bf16 [B][T][NH*D] views with row pitches,
+// float32 lse / delta [B][NH][T]; D = 32, 64 or 128
+int hvk_attn_tile(int which);
+int hvk_attn_fwd(const void* q, long long ldq, const void* k, long long ldk,
+                 const void* v, long long ldv, void* o, long long ldo,
+                 float* lse, int B, int T, int NH, int D, int causal,
+                 hipStream_t s);
+int hvk_attn_bwd_delta(const void* dout, long long lddo, const void* o,
+                       long long ldo, float* delta, int B, int T, int NH,
+                       int D, hipStream_t s);
+int hvk_attn_bwd_dkv(const void* q, long long ldq, const void* k,
+                     long long ldk, const void* v, long long ldv,
+                     const void* dout, long long lddo, const float* lse,
+                     const float* delta, void* dk, long long lddk, void* dv,
+                     long long lddv, int B, int T, int NH, int D, int causal,
+                     hipStream_t s);
+int hvk_attn_bwd_dq(const void* q, long long ldq, const void* k,
+                    long long ldk, const void* v, long long ldv,
+                    const void* dout, long long lddo, const float* lse,
+                    const float* delta, void* dq, long long lddq, int B, int T,
+                    int NH, int D, int causal, hipStream_t s);
 int hvk_act_fwd(const void* x, int xdt, void* y, int ydt, long long n, int act,
                 hipStream_t s);
 int hvk_softmax_ce(const void* logits, int in_dt, int B, int C,

@@ -13,6 +13,7 @@ from veles_amd.models.decision import *  # noqa: F401,F403
 from veles_amd.models.lr_adjust import *  # noqa: F401,F403
 from veles_amd.models.kohonen import *  # noqa: F401,F403
 from veles_amd.models.recurrent import *  # noqa: F401,F403
+from veles_amd.models.attention import *  # noqa: F401,F403
 from veles_amd.models.rbm import *  # noqa: F401,F403
 from veles_amd.models.standard_workflow import (  # noqa: F401
     StandardWorkflow, LAYER_TYPES, parse_mcdnnic)

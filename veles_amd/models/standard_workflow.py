@@ -26,6 +26,7 @@ from veles_amd.accelerated_units import AcceleratedWorkflow
 from veles_amd.loader.base import UserLoaderRegistry
 from veles_amd.models import activation as act_units
 from veles_amd.models import batch_norm as bn_units
+from veles_amd.models.attention import Attention, GDAttention
 from veles_amd.models.all2all import (
     All2All, All2AllRELU, All2AllSigmoid, All2AllSoftmax, All2AllStrictRELU,
     All2AllTanh, ResizableAll2All)
@@ -93,6 +94,7 @@ LAYER_TYPES = {
     "lstm": (LSTM, GDLSTM),
     "rnn": (RNN, GDRNN),
     "gru": (GRU, GDGRU),
+    "attention": (Attention, GDAttention),
     "norm": (LRNormalizerForward, LRNormalizerBackward),
     "batch_norm": (bn_units.BatchNorm, bn_units.GDBatchNorm),
     "batch_norm_tanh": (bn_units.BatchNormTanh, bn_units.GDBatchNormTanh),
@@ -118,7 +120,7 @@ LAYER_TYPES = {
 # GD classes whose err_input kernel can multiply by f'(aux) in its epilogue
 _FUSABLE = (GradientDescent, GradientDescentConv, GDMaxPooling, GDAvgPooling,
             GDMaxAbsPooling, LRNormalizerBackward, DropoutBackward,
-            act_units.ActivationBackward, bn_units.GDBatchNorm)
+            act_units.ActivationBackward, bn_units.GDBatchNorm, GDAttention)
 _POOL_KW = ("kx", "ky", "sliding")
 _LRN_KW = ("alpha", "beta", "k", "n")
 

@@ -33,7 +33,8 @@ __all__ = ["ACT", "gemm", "linear_fwd", "conv_out_size", "conv_fwd",
            "mean_disp_normalize", "act_code", "kohonen_coords",
            "kohonen_argmin", "kohonen_update", "lstm_fwd", "lstm_bwd",
            "rbm_layout", "rbm_uniforms", "rbm_sample", "rbm_grad",
-           "bn_partials", "batchnorm_fwd", "batchnorm_bwd"]
+           "bn_partials", "batchnorm_fwd", "batchnorm_bwd", "attention_fwd",
+           "attention_bwd", "mha_fwd", "mha_bwd", "attn_head_dim"]
 
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2, torch.int32: 3,
       torch.float16: 4}
@@ -3872,3 +3873,397 @@ def rbm_grad(v0, h0, vk, hk, grad, *, n=None, scale=None, splits=0):
     grad[off_hb:off_hb + H] = scale * (a0 - ak).sum(0)
     grad[off_vb:off_vb + V] = scale * (b0 - bk).sum(0)
     return grad
+
+
+# ------------------------------------------------------------ self-attention
+# docs/OPS.md "Attention".  Head widths the kernels are built for, and the
+# rows a workgroup owns / sweeps per tile (csrc/kernels/attention.hip).
+ATTN_HEAD_DIMS = (32, 64, 128)
+ATTN_TQ = 128
+ATTN_TK = 32
+
+
+def _attn_fn(name):
+    fn = getattr(_lib.lib(), name, None)
+    if fn is None:
+        raise _lib.KernelLibraryMissing(
+            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
+            (_lib.LIB_PATH, name))
+    return fn
+
+
+def attn_head_dim(E, heads, name="attention"):
+    """D = E / heads, checked against the supported head widths (the same
+    check on every device, so a config that runs on the CPU runs on the GPU)"""
+    E, heads = int(E), int(heads)
+    if heads < 1 or E < 1 or E % heads:
+        raise ValueError("%s: width %d does not split into %d heads" %
+                         (name, E, heads))
+    D = E // heads
+    if D not in ATTN_HEAD_DIMS:
+        raise ValueError("%s: head width %d (= %d / %d heads) is not "
+                         "supported; supported head widths are %s" %
+                         (name, D, E, heads, list(ATTN_HEAD_DIMS)))
+    return D
+
+
+def _attn_view(name, what, t, like=None):
+    """(B, T, E, pitch) of a [B][T][E] view with contiguous rows and one row
+    pitch over [B][T]"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: %s must be a tensor, got %s" % (
+            name, what, type(t).__name__))
+    if t.dim() != 3 or min(t.shape) < 1:
+        raise ValueError("%s: %s must be [B][T][E], got %s" %
+                         (name, what, tuple(t.shape)))
+    B, T, E = t.shape
+    ld = t.stride(1) if B * T > 1 else max(t.stride(1), E)
+    if t.stride(2) != 1 or ld < E or (B > 1 and t.stride(0) != T * ld):
+        raise ValueError("%s: %s rows must be contiguous with one pitch over "
+                         "[B][T] (strides %s)" % (name, what, t.stride()))
+    if B * T * ld >= 1 << 31:
+        raise ValueError("%s: %s spans %d x %d x %d elements, the limit is "
+                         "2^31 - 1" % (name, what, B, T, ld))
+    if like is not None:
+        if tuple(t.shape) != tuple(like.shape):
+            raise ValueError("%s: %s is %s, q is %s" % (
+                name, what, tuple(t.shape), tuple(like.shape)))
+        if t.dtype != like.dtype:
+            raise TypeError("%s: %s is %s, q is %s" % (
+                name, what, t.dtype, like.dtype))
+        if t.device != like.device:
+            raise ValueError("%s: %s is on %s, q on %s" % (
+                name, what, t.device, like.device))
+    return B, T, E, ld
+
+
+def _attn_dtype(name, q):
+    if _gpu(q):
+        if q.dtype != torch.bfloat16:
+            raise TypeError("%s: GPU operands must be bfloat16, got %s" %
+                            (name, q.dtype))
+        if q.data_ptr() % 2:
+            raise ValueError("%s: operands off the element grid" % name)
+    elif q.dtype != torch.float32:
+        raise TypeError("%s: CPU operands must be float32, got %s" %
+                        (name, q.dtype))
+
+
+def _attn_stat(name, what, t, B, NH, T, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or \
+            tuple(t.shape) != (B, NH, T) or not t.is_contiguous() or \
+            t.device != dev:
+        raise ValueError("%s: %s must be a contiguous float32 [%d][%d][%d] "
+                         "on %s" % (name, what, B, NH, T, dev))
+
+
+def _attn_heads(t, NH, D):
+    """[B][T][NH*D] -> [B][NH][T][D] view"""
+    B, T, _ = t.shape
+    return t.reshape(B, T, NH, D).permute(0, 2, 1, 3)
+
+
+def _attn_mask(T, dev):
+    """True where key j is hidden from query i (j > i)"""
+    i = torch.arange(T, device=dev)
+    return i.view(1, T) > i.view(T, 1)
+
+
+def attention_fwd(q, k, v, heads, causal=False, out=None, save=None):
+    """Scaled dot-product self-attention over ``heads`` heads.
+
+    ``q``, ``k``, ``v`` are [B][T][E] views with contiguous rows and a row
+    pitch each (column slices of one fused projection buffer need no copy);
+    head h is columns h*D .. (h+1)*D - 1, D = E / heads in (32, 64, 128).
+    Per (batch, head): S = q k^T / sqrt(D); with ``causal`` key j is visible
+    to query i iff j <= i; P = softmax_j(S); o = P v.  Returns o [B][T][E]
+    (``out`` when given); ``save`` (a dict) receives "lse" = ln sum_j
+    exp(S_ij), float32 [B][heads][T], for :func:`attention_bwd`.
+
+    GPU: bfloat16 operands, ``hvk_attn_fwd`` (flash style: no [T][T] tensor
+    in memory) on the current stream.  CPU: float32, S materialised per
+    (batch, head) with the row maximum subtracted."""
+    name = "attention_fwd"
+    B, T, E, ldq = _attn_view(name, "q", q)
+    _attn_dtype(name, q)
+    _, _, _, ldk = _attn_view(name, "k", k, like=q)
+    _, _, _, ldv = _attn_view(name, "v", v, like=q)
+    NH = int(heads)
+    D = attn_head_dim(E, NH, name)
+    dev = q.device
+    if out is None:
+        out = torch.empty(B, T, E, dtype=q.dtype, device=dev)
+    _, _, _, ldo = _attn_view(name, "out", out, like=q)
+    save = {} if save is None else save
+    lse = _rec_buf(save, "lse", (B, NH, T), torch.float32, dev)
+    if _gpu(q):
+        _lib.check(_attn_fn("hvk_attn_fwd")(
+            _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, _p(lse), B, T,
+            NH, D, int(bool(causal)), _s(q)), "hvk_attn_fwd")
+        return out
+    qh, kh, vh = (_attn_heads(t, NH, D) for t in (q, k, v))
+    s = (qh @ kh.transpose(2, 3)) * (1.0 / math.sqrt(D))
+    if causal:
+        s = s.masked_fill(_attn_mask(T, dev), float("-inf"))
+    m = s.max(dim=3, keepdim=True).values
+    e = torch.exp(s - m)
+    l = e.sum(dim=3, keepdim=True)
+    lse.copy_((m + torch.log(l)).squeeze(3))
+    o = (e / l) @ vh
+    out.copy_(o.permute(0, 2, 1, 3).reshape(B, T, E))
+    return out
+
+
+def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
+                  dk=None, dv=None, ws=None):
+    """Backward of :func:`attention_fwd` from its ``save`` ("lse"): returns
+    (dq, dk, dv), each [B][T][E] (the given views, e.g. column slices of one
+    fused gradient buffer, or new tensors).
+
+        P = exp(S - lse),  dV = P^T dO,  dP = dO V^T,
+        delta = rowsum(dO * O),  dS = P * (dP - delta) / sqrt(D),
+        dQ = dS K,  dK = dS^T Q
+
+    GPU: ``hvk_attn_bwd_delta``, ``hvk_attn_bwd_dkv`` and ``hvk_attn_bwd_dq``
+    (P recomputed from lse in both; no atomics, the result repeats bit for
+    bit); ``ws`` (a dict) keeps "delta".  CPU: float32."""
+    name = "attention_bwd"
+    B, T, E, ldq = _attn_view(name, "q", q)
+    _attn_dtype(name, q)
+    _, _, _, ldk = _attn_view(name, "k", k, like=q)
+    _, _, _, ldv = _attn_view(name, "v", v, like=q)
+    _, _, _, ldo = _attn_view(name, "o", o, like=q)
+    _, _, _, lddo = _attn_view(name, "do", do, like=q)
+    NH = int(heads)
+    D = attn_head_dim(E, NH, name)
+    dev = q.device
+    if not isinstance(save, dict) or "lse" not in save:
+        raise ValueError("%s: save must be attention_fwd's dict" % name)
+    lse = save["lse"]
+    _attn_stat(name, "save[\"lse\"]", lse, B, NH, T, dev)
+    grads = []
+    for what, t in (("dq", dq), ("dk", dk), ("dv", dv)):
+        if t is None:
+            t = torch.empty(B, T, E, dtype=q.dtype, device=dev)
+        grads.append((t, _attn_view(name, what, t, like=q)[3]))
+    (dq, lddq), (dk, lddk), (dv, lddv) = grads
+    ws = {} if ws is None else ws
+    delta = _rec_buf(ws, "delta", (B, NH, T), torch.float32, dev)
+    c = int(bool(causal))
+    if _gpu(q):
+        s = _s(q)
+        _lib.check(_attn_fn("hvk_attn_bwd_delta")(
+            _p(do), lddo, _p(o), ldo, _p(delta), B, T, NH, D, s),
+            "hvk_attn_bwd_delta")
+        _lib.check(_attn_fn("hvk_attn_bwd_dkv")(
+            _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
+            _p(delta), _p(dk), lddk, _p(dv), lddv, B, T, NH, D, c, s),
+            "hvk_attn_bwd_dkv")
+        _lib.check(_attn_fn("hvk_attn_bwd_dq")(
+            _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
+            _p(delta), _p(dq), lddq, B, T, NH, D, c, s), "hvk_attn_bwd_dq")
+        return dq, dk, dv
+    scale = 1.0 / math.sqrt(D)
+    qh, kh, vh, oh, doh = (_attn_heads(t, NH, D) for t in (q, k, v, o, do))
+    s = (qh @ kh.transpose(2, 3)) * scale
+    p = torch.exp(s - lse.unsqueeze(3))
+    if causal:
+        p = p.masked_fill(_attn_mask(T, dev), 0.0)
+    delta.copy_((doh * oh).sum(3))
+    dp = doh @ vh.transpose(2, 3)
+    ds = p * (dp - delta.unsqueeze(3)) * scale
+    for t, g in ((dq, ds @ kh), (dk, ds.transpose(2, 3) @ qh),
+                 (dv, p.transpose(2, 3) @ doh)):
+        t.copy_(g.permute(0, 2, 1, 3).reshape(B, T, E))
+    return dq, dk, dv
+
+
+def _mha_args(name, x, w_in, w_out, bias, heads):
+    """Shared host checks of mha_fwd / mha_bwd; returns (B, T, I, E, D)"""
+    for what, t in (("x", x), ("w_in", w_in), ("w_out", w_out)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a tensor, got %s" % (
+                name, what, type(t).__name__))
+    if x.dim() != 3 or min(x.shape) < 1:
+        raise ValueError("%s: input must be [B][T][I], got %s" %
+                         (name, tuple(x.shape)))
+    B, T, I = x.shape
+    if w_out.dim() != 2 or w_out.shape[0] != w_out.shape[1]:
+        raise ValueError("%s: w_out must be [E][E], got %s" %
+                         (name, tuple(w_out.shape)))
+    E = w_out.shape[0]
+    D = attn_head_dim(E, heads, name)
+    if w_in.dim() != 2 or tuple(w_in.shape) != (3 * E, I):
+        raise ValueError("%s: w_in must be [%d][%d] (rows q, k, v; E = %d, "
+                         "I = %d), got %s" % (name, 3 * E, I, E, I,
+                                              tuple(w_in.shape)))
+    if w_in.device != x.device or w_out.device != x.device or \
+            (bias is not None and bias.device != x.device):
+        raise ValueError("%s: operands on different devices" % name)
+    if x.stride(2) != 1 or (B * T > 1 and x.stride(1) < I) or \
+            (B > 1 and x.stride(0) != T * x.stride(1)) or \
+            w_in.stride(1) != 1 or w_out.stride(1) != 1:
+        raise ValueError("%s: input rows must be contiguous with one pitch "
+                         "over [B][T], weight rows contiguous (strides %s, "
+                         "%s, %s)" % (name, x.stride(), w_in.stride(),
+                                      w_out.stride()))
+    if bias is not None and (tuple(bias.shape) != (4 * E,) or
+                             not bias.is_contiguous()):
+        raise ValueError("%s: bias must be a contiguous [%d] = (b_q, b_k, "
+                         "b_v, b_o), got %s" % (name, 4 * E,
+                                                tuple(bias.shape)))
+    if _gpu(x):
+        if x.dtype != torch.bfloat16 or w_in.dtype != torch.bfloat16 or \
+                w_out.dtype != torch.bfloat16:
+            raise TypeError("%s: GPU input and weights must be bfloat16, got "
+                            "%s / %s / %s" % (name, x.dtype, w_in.dtype,
+                                              w_out.dtype))
+        if bias is not None and bias.dtype != torch.float32:
+            raise TypeError("%s: GPU bias must be float32, got %s" %
+                            (name, bias.dtype))
+    elif not (x.is_floating_point() and w_in.is_floating_point() and
+              w_out.is_floating_point()):
+        raise TypeError("%s: floating-point operands, got %s / %s / %s" %
+                        (name, x.dtype, w_in.dtype, w_out.dtype))
+    if B * T * max(3 * E, x.stride(1) if B * T > 1 else I) >= 1 << 31:
+        raise ValueError("%s: %d x %d x %d exceeds 2^31 elements" %
+                         (name, B, T, max(3 * E, I)))
+    return B, T, I, E, D
+
+
+def _mha_rows(x, B, T):
+    return x.as_strided((B * T, x.shape[2]),
+                        (x.stride(1) if B * T > 1 else x.shape[2], 1))
+
+
+def mha_fwd(x, w_in, w_out, bias, heads, *, causal=False, save=None,
+            ws=None, out=None):
+    """Multi-head self-attention layer over ``x`` [B][T][I] (batch-major):
+    ``torch.nn.MultiheadAttention(E, heads, bias=True, batch_first=True)``
+    applied to (x, x, x).
+
+        qkv = x w_in^T + bias[:3E]      w_in [3E][I], rows q, k, v, each
+                                        block head-major
+        o   = attention(q, k, v)        :func:`attention_fwd`
+        y   = o w_out^T + bias[3E:]     w_out [E][E]
+
+    ``bias`` is [4E] or None.  Returns y [B][T][E] (``out`` when given).
+    ``save`` (a dict) receives "qkv" [B*T][3E], "o" [B][T][E] and "lse" for
+    :func:`mha_bwd`; q, k and v are column slices of "qkv": no head
+    transposes, no copies.  A kept ``save`` / ``ws`` dict is reused: no
+    allocation from the second call on."""
+    name = "mha_fwd"
+    B, T, I, E, D = _mha_args(name, x, w_in, w_out, bias, heads)
+    dev = x.device
+    st = save if save is not None else (ws if ws is not None else {})
+    dt = torch.bfloat16 if _gpu(x) else torch.float32
+    if out is not None and (tuple(out.shape) != (B, T, E) or
+                            not out.is_contiguous() or out.device != dev or
+                            out.dtype != dt):
+        raise ValueError("%s: out must be a contiguous %s [%d][%d][%d] on %s"
+                         % (name, dt, B, T, E, dev))
+    if out is None:
+        out = torch.empty(B, T, E, dtype=dt, device=dev)
+    qkv = _rec_buf(st, "qkv", (B * T, 3 * E), dt, dev)
+    o = _rec_buf(st, "o", (B, T, E), dt, dev)
+    b_in = None if bias is None else bias[:3 * E]
+    b_out = None if bias is None else bias[3 * E:]
+    x2 = _mha_rows(x, B, T)
+    if _gpu(x):
+        gemm(x2, w_in, trans_b=True, bias=b_in, out=qkv)
+    else:
+        r = x2.float() @ w_in.float().t()
+        qkv.copy_(r if b_in is None else r + b_in.float())
+    q3 = qkv.view(B, T, 3 * E)
+    attention_fwd(q3[:, :, :E], q3[:, :, E:2 * E], q3[:, :, 2 * E:], heads,
+                  causal=causal, out=o, save=st)
+    if _gpu(x):
+        gemm(o.view(B * T, E), w_out, trans_b=True, bias=b_out,
+             out=out.view(B * T, E))
+    else:
+        r = o.view(B * T, E) @ w_out.float().t()
+        out.view(B * T, E).copy_(r if b_out is None else r + b_out.float())
+    return out
+
+
+def mha_bwd(err, x, w_in, w_out, save, dw_in, dw_out, dbias, heads, *,
+            causal=False, accumulate="overwrite", need_err_input=True,
+            err_input=None, aux=None, aux_act=0):
+    """Backward of :func:`mha_fwd` from its ``save`` dict.  ``err`` is dL/dy
+    [B][T][E].
+
+        dw_out (+)= err^T o, dbias[3E:] (+)= its column sums (one GEMM)
+        do = err w_out;  (dq | dk | dv) = attention_bwd, into one fused
+        [B*T][3E] buffer save["dqkv"]
+        dw_in (+)= dqkv^T x, dbias[:3E] (+)= its column sums
+        err_input [B][T][I] = dqkv w_in, times f'(aux) of the layer below
+        when ``aux_act`` is set (the GEMM's epilogue)
+
+    ``dw_in`` float32 [3E][I], ``dw_out`` float32 [E][E], ``dbias`` float32
+    [4E] or None; ``accumulate``: True adds, "overwrite" writes, as in
+    ``gemm``.  Returns err_input (None without ``need_err_input``)."""
+    name = "mha_bwd"
+    B, T, I, E, D = _mha_args(name, x, w_in, w_out, None, heads)
+    dev = x.device
+    gpu = _gpu(x)
+    dt = torch.bfloat16 if gpu else torch.float32
+    if accumulate not in (True, "overwrite"):
+        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
+                         name)
+    if not isinstance(err, torch.Tensor) or \
+            tuple(err.shape) != (B, T, E) or not err.is_contiguous() or \
+            err.device != dev:
+        raise ValueError("%s: err must be a contiguous [%d][%d][%d] on %s" %
+                         (name, B, T, E, dev))
+    if gpu and err.dtype != torch.bfloat16:
+        raise TypeError("%s: GPU err must be bfloat16, got %s" %
+                        (name, err.dtype))
+    for what, t, shape in (("dw_in", dw_in, (3 * E, I)),
+                           ("dw_out", dw_out, (E, E))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or \
+                tuple(t.shape) != shape or not t.is_contiguous() or \
+                t.device != dev:
+            raise ValueError("%s: %s must be a contiguous float32 [%d][%d] "
+                             "on %s" % (name, what, shape[0], shape[1], dev))
+    if dbias is not None and (dbias.dtype != torch.float32 or
+                              tuple(dbias.shape) != (4 * E,) or
+                              not dbias.is_contiguous() or
+                              dbias.device != dev):
+        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
+                         % (name, 4 * E, dev))
+    NH = int(heads)
+    _rec_save_check(name, "mha_fwd", save,
+                    (("qkv", (B * T, 3 * E), dt), ("o", (B, T, E), dt),
+                     ("lse", (B, NH, T), torch.float32)), dev)
+    aux_act = act_code(aux_act)
+    if aux_act and aux is None:
+        raise ValueError("%s: aux_act without aux" % name)
+    if need_err_input:
+        _rec_err_input_check(name, err_input, B, T, I, dt, dev)
+        if aux_act and (aux.numel() != B * T * I or not aux.is_contiguous()):
+            raise ValueError("%s: aux must be a contiguous [%d][%d][%d]" %
+                             (name, B, T, I))
+    err2 = err.view(B * T, E) if gpu else err.float().view(B * T, E)
+    o2 = save["o"].view(B * T, E)
+    x2 = _mha_rows(x, B, T) if gpu else _mha_rows(x, B, T).float()
+    wi, wo = (w_in, w_out) if gpu else (w_in.float(), w_out.float())
+    db_in = None if dbias is None else dbias[:3 * E]
+    db_out = None if dbias is None else dbias[3 * E:]
+    gemm(err2, o2, trans_a=True, out=dw_out, accumulate=accumulate,
+         bias_grad=db_out)
+    do = _rec_buf(save, "do", (B, T, E), dt, dev)
+    gemm(err2, wo, out=do.view(B * T, E))
+    dqkv = _rec_buf(save, "dqkv", (B * T, 3 * E), dt, dev)
+    q3, g3 = save["qkv"].view(B, T, 3 * E), dqkv.view(B, T, 3 * E)
+    attention_bwd(do, q3[:, :, :E], q3[:, :, E:2 * E], q3[:, :, 2 * E:],
+                  save["o"], save, heads, causal=causal, dq=g3[:, :, :E],
+                  dk=g3[:, :, E:2 * E], dv=g3[:, :, 2 * E:], ws=save)
+    gemm(dqkv, x2, trans_a=True, out=dw_in, accumulate=accumulate,
+         bias_grad=db_in)
+    if not need_err_input:
+        return None
+    if err_input is None:
+        err_input = torch.empty(B, T, I, dtype=dt, device=dev)
+    gemm(dqkv, wi, out=err_input.view(B * T, I),
+         aux=aux.reshape(B * T, I) if aux_act else None, aux_act=aux_act)
+    return err_input

@@ -184,6 +184,16 @@ _OPTIONAL = {
     "hvk_bn_fold": [P, P, P, P, I, F, P, P],
     "hvk_bn_apply": [P, L, P, L, L, I, P, I, P],
     "hvk_bn_bwd": [P, L] * 5 + [L, I, I, P, P, P, P, P, I, I, I, P, P, P],
+    # self-attention (csrc/kernels/attention.hip), every bf16 [B][T][NH*D]
+    # view followed by its row pitch: (which); (q, k, v, o, lse, B, T, NH, D,
+    # causal, s); (do, o, delta, B, T, NH, D, s); (q, k, v, do, lse, delta,
+    # dk, dv, B, T, NH, D, causal, s); (q, k, v, do, lse, delta, dq, B, T,
+    # NH, D, causal, s)
+    "hvk_attn_tile": [I],
+    "hvk_attn_fwd": [P, L] * 4 + [P, I, I, I, I, I, P],
+    "hvk_attn_bwd_delta": [P, L] * 2 + [P, I, I, I, I, P],
+    "hvk_attn_bwd_dkv": [P, L] * 4 + [P, P] + [P, L] * 2 + [I, I, I, I, I, P],
+    "hvk_attn_bwd_dq": [P, L] * 4 + [P, P] + [P, L] + [I, I, I, I, I, P],
 }
 # functions returning a pointer / a 64-bit int (every other one returns int)
 _PTR_RET = {"hvk_stream_create"}
