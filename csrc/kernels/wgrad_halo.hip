@@ -85,6 +85,15 @@ __device__ __forceinline__ int a_sw(int r) {
 
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 
+// dma16 to an LDS-address-space pointer: the target keeps the identity of
+// the __shared__ object it points into (what the waitcnt insertion needs to
+// tell a stage being filled from the stage being read)
+__device__ __forceinline__ void dma16l(__amdgpu_buffer_rsrc_t r, lds_u8* lds,
+                                       uint32_t voff) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(
+      r, (__attribute__((address_space(3))) void*)lds, 16, voff, 0, 0, 0);
+}
+
 // two transposed 8-B reads (k rows of this lane's pixel, +16 pixels) ->
 // one 16x16x32 operand fragment; o0 / o1 are LDS byte offsets
 __device__ __forceinline__ bf16x8 tr_read(lds_u8* sm, uint32_t o0,
@@ -125,8 +134,25 @@ __device__ __forceinline__ bf16x8 tr_read(lds_u8* sm, uint32_t o0,
 //   * the segment form splits slot j = aj * Wp + bj the same way.
 // Barriers, waits, the pixel-to-k mapping and the MFMA order are those of
 // the old loop: results are bit-identical.
+// STG (hvk_halo_stages, default on, LEAN only; off is the lean loop with
+// both stages in one array, kept for A/B and the bitwise tests): each stage
+// is an LDS object of its own and the pixel loop runs two steps per turn,
+// so every DMA target and every fragment read names its array at compile
+// time.  With one array and a run-time stage offset hipcc cannot tell that
+// the next step's DMA (stage nxt) and this step's transposed reads (stage
+// cur) are disjoint and puts an s_waitcnt vmcnt(0) in front of the first
+// read: a wave then starts a step's MFMAs only after its own pieces of the
+// NEXT stage have landed.  With two objects it places no such wait (it
+// still would if a read could alias the DMA target).  The step's own
+// vmcnt(0) + s_barrier at its end (through the builtin, so that hipcc knows
+// of it), the DMA pieces and the pixel-to-k mapping are unchanged, and each
+// accumulator takes the same MFMAs in the same order (k half 0, then 1; the
+// two of an n-tile now back to back, see step()): results are
+// bit-identical.  Two step bodies cost registers the one-array loop (253 of
+// 256) does not have: the lane invariants are packed or recomputed where
+// marked STG, and the bias MFMAs run in wave column 1.
 template <int MT, int NP, int KHT, int KW, int NJW, int PB, bool SEG,
-          bool LEAN>
+          bool LEAN, bool STG>
 __global__ void __launch_bounds__(256, 2)
 wgrad_halo_kernel(const uint16_t* __restrict__ x,
                   const uint16_t* __restrict__ dy, float* __restrict__ ws,
@@ -146,7 +172,12 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
   constexpr int NBW = (NB + 3) / 4;
   constexpr int STAGE = ABYTES + NB * 1024;
   static_assert(2 * 2 * STAGE <= 160 * 1024, "two workgroups per CU");
-  __shared__ __attribute__((aligned(16))) uint8_t smem[2 * STAGE];
+  static_assert(LEAN || !STG, "the two-object stages are the lean loop's");
+  static_assert(STAGE % 1024 == 0, "whole DMA pieces per stage");
+  // STG: stage 0 and stage 1; else both stages in smem (smem1 unused)
+  __shared__ __attribute__((aligned(1024))) uint8_t
+      smem[STG ? STAGE : 2 * STAGE];
+  __shared__ __attribute__((aligned(1024))) uint8_t smem1[STG ? STAGE : 16];
 
   const int wgid = xcd_remap(blockIdx.x, gridDim.x);
   const int tile = wgid % tiles;
@@ -334,6 +365,11 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
   // l_inv its byte offset less the step's scalar base; l_bj (SEG) bj
   constexpr int kNoRow = 0x40000000;
   int l_rs[NBW], l_bj[NBW];
+  // STG, SEG: both in one register, bj | row << 16; all ones where the
+  // lane loads nothing: row 0xffff fails the row test unless H > 65000,
+  // and then W < 2^26 / H (the tensor spans < 2 GiB at >= 16 channels) and
+  // column 0xffff fails the column test
+  uint32_t l_pk[NBW];
   uint32_t l_inv[NBW];
   // pixel q + 16 i = a_i * OW + b_i: l_b = b_i, l_k = the stage byte of
   // window slot a_i * Wp + b_i (+ this lane's trp * 8)
@@ -349,10 +385,12 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
         const int r = b_rs[i] + (int)aj;
         l_bj[i] = bj;
         l_rs[i] = b_ok[i] ? r : kNoRow;
+        l_pk[i] = b_ok[i] ? (uint32_t)bj | (uint32_t)r << 16 : 0xffffffffu;
         l_inv[i] = (uint32_t)r * rowbytes + (uint32_t)(bj - g.pl) * pixbytes +
                    b_col[i];
       } else {
         l_bj[i] = 0;
+        l_pk[i] = 0;
         l_rs[i] = b_ok[i] ? b_rs[i] : kNoRow;
         l_inv[i] = (uint32_t)b_rs[i] * rowbytes + b_col[i];
       }
@@ -364,6 +402,13 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
       const uint32_t b = c - a * (uint32_t)g.OW;
       l_b[i] = (int)b;
       l_k[i] = (a * (uint32_t)g.Wp + b) * 32u + (uint32_t)(trp * 8 + ABYTES);
+      // (pinned: else hipcc keeps the slot term and adds the rest in front
+      // of each of the three loops, one more register per pixel up to there)
+      // STG: b_i rides in the upper half of l_k (stage bytes < 2^16)
+      if constexpr (STG) {
+        l_k[i] |= b << 16;
+        asm volatile("" : "+v"(l_k[i]));
+      }
     }
   }
   // a step's scalars.  base: byte offset of input row oh + kh0 - pt of image
@@ -396,17 +441,22 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
     s.plim = SEG ? g.OHW - (int)pin0 : pend - (int)p;
     return s;
   };
-  auto lean_issue = [&](const LeanStep& s, uint8_t* st) {
+  auto lean_issue = [&](const LeanStep& s, lds_u8* st) {
     if constexpr ((HVK_HALO_ABL & 1) != 0) return;
     if (s.plim >= 64) {   // wave-uniform: every dY row of the step is valid
 #pragma unroll
       for (int i = 0; i < NAW; ++i)
-        dma16(ra, st + (w * NAW + i) * 1024, s.pa + a_off[i]);
+        dma16l(ra, st + (w * NAW + i) * 1024, s.pa + a_off[i]);
     } else {
+      int la = lane;
+      if constexpr (STG) asm volatile("" : "+v"(la));
 #pragma unroll
       for (int i = 0; i < NAW; ++i) {
-        const uint32_t v = (a_row[i] < s.plim) ? s.pa + a_off[i] : kBufOOB;
-        dma16(ra, st + (w * NAW + i) * 1024, v);
+        // STG: the row from the lane again on this rare path (la opaque, so
+        // that it stays here), not from NAW registers held through the loop
+        const int r = STG ? ((w * NAW + i) * 1024 + 16 * la) / AP : a_row[i];
+        const uint32_t v = (r < s.plim) ? s.pa + a_off[i] : kBufOOB;
+        dma16l(ra, st + (w * NAW + i) * 1024, v);
       }
     }
     if constexpr (SEG) {
@@ -424,17 +474,19 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
           live = i < nb;   // wave-uniform
         }
         if (live) {
-          const int t = l_bj[i] + (int)s.ow;
+          const int bj = STG ? (int)(l_pk[i] & 0xffffu) : l_bj[i];
+          const int rs = STG ? (int)(l_pk[i] >> 16) : l_rs[i];
+          const int t = bj + (int)s.ow;
           const bool c = t >= g.Wp;
           const uint32_t iw = (uint32_t)(t - (c ? g.Wp + g.pl : g.pl));
-          const uint32_t ih = (uint32_t)(l_rs[i] + ihb + (c ? 1 : 0));
+          const uint32_t ih = (uint32_t)(rs + ihb + (c ? 1 : 0));
           uint32_t a = l_inv[i] + s.base + (c ? wrapb : 0u);
           // (pinned, and no short circuit: else hipcc sinks the offset into
           // an exec-masked region per piece)
           asm("" : "+v"(a));
           const bool ok = (iw < cw) & (ih < (uint32_t)g.H);
           const uint32_t v = ok ? a : kBufOOB;
-          dma16(rb, st + ABYTES + (w + 4 * i) * 1024, v);
+          dma16l(rb, st + ABYTES + (w + 4 * i) * 1024, v);
         }
       }
       return;
@@ -460,7 +512,7 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
         const int rs = l_rs[i];
         uint32_t v = (uint32_t)(rs - bl) < bn ? l_inv[i] + base_b : kBufOOB;
         v = (uint32_t)(rs - a_lo) < a_len ? l_inv[i] + s.base : v;
-        dma16(rb, st + ABYTES + (w + 4 * i) * 1024, v);
+        dma16l(rb, st + ABYTES + (w + 4 * i) * 1024, v);
       }
     }
   };
@@ -493,15 +545,29 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
     }
   };
 
+  // the stage-end wait, vmcnt(0).  STG: the same instruction through the
+  // builtin (0x0f70: vmcnt 0, expcnt and lgkmcnt untouched) - the waitcnt
+  // insertion does not look into an asm, would still count the DMA of the
+  // previous body as pending at the first fragment read of the stage it
+  // filled, and wait for it behind the DMA this body has just issued
+  auto stage_wait = [&]() {
+    if constexpr (STG) {
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_s_waitcnt(0x0f70);
+      asm volatile("" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  };
   const int nk = SEG ? pend - pbeg : (pend - pbeg + 63) >> 6;
   LeanStep lc{}, ln{};   // the step in the MFMAs, the step being loaded
   if constexpr (LEAN) {
     lc = lean_first();
-    lean_issue(lc, smem);
+    lean_issue(lc, sm);
   } else {
     issue(n0, pin0, oh0, ow0, smem);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  stage_wait();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 
@@ -513,16 +579,34 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
     advance(nn, pinn, ohn, own);
   }
 
-  const bool bwave = bias && kg == 0 && cc == 0 && wc == 0;
+  // the bias MFMAs run in wave column 0; STG: in column 1, which has the
+  // fewer n-tiles where they are odd (AlexNet conv1: 13 against 14, room
+  // for the MI bias accumulators; the same dY fragments, the same sums)
+  constexpr int BWC = STG ? 1 : 0;
+  const bool bwave = bias && kg == 0 && cc == 0 && wc == BWC;
 
   auto main_loop = [&](auto wcc, auto with_bias) {
     constexpr int WC = decltype(wcc)::value;
     constexpr bool WB = decltype(with_bias)::value;
-    for (int kt = 0; kt < nk; ++kt) {
-      const uint32_t cur = (kt & 1) * STAGE;
-      if (kt + 1 < nk) {
-        if constexpr (LEAN) lean_issue(ln, smem + ((kt + 1) & 1) * STAGE);
-        else issue(nn, pinn, ohn, own, smem + ((kt + 1) & 1) * STAGE);
+    // one pixel step.  PAR: the parity of step kt, a compile-time constant
+    // in the STG loop (its stage is then the array sc at offset 0, the next
+    // step's the other array); more: a step follows
+    auto step = [&](auto par, int kt, bool more) {
+      constexpr int PAR = decltype(par)::value;
+      const uint32_t cur = STG ? 0 : (kt & 1) * STAGE;
+      lds_u8* sc;
+      if constexpr (!STG) sc = sm;
+      else if constexpr (PAR == 0) sc = (lds_u8*)smem;
+      else sc = (lds_u8*)smem1;
+      if (more) {
+        if constexpr (STG) {
+          if constexpr (PAR == 0) lean_issue(ln, (lds_u8*)smem1);
+          else lean_issue(ln, (lds_u8*)smem);
+        } else if constexpr (LEAN) {
+          lean_issue(ln, sm + ((kt + 1) & 1) * STAGE);
+        } else {
+          issue(nn, pinn, ohn, own, smem + ((kt + 1) & 1) * STAGE);
+        }
       }
       // B fragment bases (LDS bytes) of this lane's 4 pixels (q + 16 i)
       // for every kh of the tap group
@@ -539,7 +623,12 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
         const uint32_t wrap = cur + ABYTES + (uint32_t)(g.OH - (int)lc.oh) * wp32;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          uint32_t base = l_k[i] + (l_b[i] >= thr ? dwp : 0u);
+          uint32_t base;
+          if constexpr (STG)   // b_i >= thr on the packed word (thr >= 1)
+            base = (l_k[i] & 0xffffu) +
+                   (l_k[i] >= (uint32_t)thr << 16 ? dwp : 0u);
+          else
+            base = l_k[i] + (l_b[i] >= thr ? dwp : 0u);
           if constexpr (SEG) {
             // pixels past the image end read slot 0 (as the old loop)
             base = q < lc.plim - 16 * i ? base : (uint32_t)(trp * 8 + ABYTES);
@@ -572,13 +661,60 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
         for (int kh = 0; kh < KHT; ++kh) bb[i][kh] = base + kh * kp * 32;
       }
       }
+      if constexpr (STG) {
+        // Both k halves of an n-tile back to back (each accumulator still
+        // takes half 0, then half 1: the same sums).  With two step bodies
+        // in the loop an accumulator has three live ranges besides the
+        // loop-carried one; in the ks-major order below all of a half's
+        // tiles sit between their two MFMAs at once, the register allocator
+        // permutes them against the carried set and spills 35-150
+        // registers.  Here at most one tile is between its MFMAs.
+        bf16x8 a[2][MI];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int i = 0; i < MI; ++i) {
+            const uint32_t oa = a_frag[i] + ks * 32 * AP;
+            a[ks][i] = tr_read(sc, oa, oa + 16 * AP);
+          }
+#pragma unroll
+        for (int j = 0; j < NJW; ++j) {
+          const int jg = WC * NJW + j;
+          if (jg < NJ) {   // compile-time after unrolling (WC constant)
+            const int tl = jg / NP, pl_ = jg - (jg / NP) * NP;
+            const int khl = tl / KW, kwl = tl - (tl / KW) * KW;
+            const uint32_t off = kwl * 32 + pl_ * PB;   // bytes
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+              const bf16x8 b = tr_read(sc, bb[2 * ks][khl] + off,
+                                       bb[2 * ks + 1][khl] + off);
+              if constexpr ((HVK_HALO_ABL & 4) != 0) {
+                acc[0][j][0] += (float)b[0] + (float)a[ks][0][0];
+              } else {
+#pragma unroll
+                for (int i = 0; i < MI; ++i)
+                  acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                      b, a[ks][i], acc[i][j], 0, 0, 0);
+              }
+            }
+          }
+        }
+        if constexpr (WB) {
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+              accb[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  ones, a[ks][i], accb[i], 0, 0, 0);
+        }
+      } else {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         bf16x8 a[MI];
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
           const uint32_t oa = cur + a_frag[i] + ks * 32 * AP;
-          a[i] = tr_read(sm, oa, oa + 16 * AP);
+          a[i] = tr_read(sc, oa, oa + 16 * AP);
         }
 #pragma unroll
         for (int j = 0; j < NJW; ++j) {
@@ -587,7 +723,7 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
             const int tl = jg / NP, pl_ = jg - (jg / NP) * NP;
             const int khl = tl / KW, kwl = tl - (tl / KW) * KW;
             const uint32_t off = kwl * 32 + pl_ * PB;   // bytes
-            const bf16x8 b = tr_read(sm, bb[2 * ks][khl] + off,
+            const bf16x8 b = tr_read(sc, bb[2 * ks][khl] + off,
                                      bb[2 * ks + 1][khl] + off);
             if constexpr ((HVK_HALO_ABL & 4) != 0) {
               acc[0][j][0] += (float)b[0] + (float)a[0][0];
@@ -606,27 +742,52 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
                                                               accb[i], 0, 0, 0);
         }
       }
+      }
       // step kt + 1 landed; every read of step kt done
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      stage_wait();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       if constexpr (LEAN) {
         lc = ln;
         lean_advance(ln);
+        // opaque between the two bodies of a turn: else hipcc folds the
+        // advance into the lane invariants of the second body (a second
+        // a_off[] + astep, l_inv[] + inc64, ... in VGPRs)
+        if constexpr (STG)
+          asm volatile("" : "+s"(ln.n), "+s"(ln.pin), "+s"(ln.oh), "+s"(ln.ow),
+                            "+s"(ln.base), "+s"(ln.pa), "+s"(ln.plim));
       } else {
         ow0 = own; oh0 = ohn; n0 = nn; pin0 = pinn;
         advance(nn, pinn, ohn, own);
       }
+    };
+    constexpr std::integral_constant<int, 0> even{};
+    constexpr std::integral_constant<int, 1> odd{};
+    if constexpr (STG) {
+      // two steps per turn, an odd nk's last step after the loop
+      int kt = 0;
+      for (; kt + 1 < nk; kt += 2) {
+        step(even, kt, true);
+        step(odd, kt + 1, kt + 2 < nk);
+      }
+      if (kt < nk) step(even, kt, false);
+    } else {
+      for (int kt = 0; kt < nk; ++kt) step(even, kt, kt + 1 < nk);
     }
   };
-  if (wc == 0) {
-    if (bwave) main_loop(std::integral_constant<int, 0>{}, std::true_type{});
-    else main_loop(std::integral_constant<int, 0>{}, std::false_type{});
+  if (wc == BWC) {
+    if (bwave) main_loop(std::integral_constant<int, BWC>{}, std::true_type{});
+    else main_loop(std::integral_constant<int, BWC>{}, std::false_type{});
   } else {
-    main_loop(std::integral_constant<int, 1>{}, std::false_type{});
+    main_loop(std::integral_constant<int, 1 - BWC>{}, std::false_type{});
   }
 
   // ---- epilogue: D[n][m] quads (4 consecutive n of one m) -> slice
+  // STG: the lane's row / quad from the thread index again, so that no
+  // epilogue value holds a register through the pixel loop
+  int te = threadIdx.x;
+  if constexpr (STG) asm volatile("" : "+v"(te));
+  const int fre = STG ? te & 15 : fr, fqe = STG ? (te & 63) >> 4 : fq;
   const long long sbase = (long long)split * g.OC;
 #pragma unroll
   for (int j = 0; j < NJW; ++j) {
@@ -634,18 +795,18 @@ wgrad_halo_kernel(const uint16_t* __restrict__ x,
     if (jg >= NJ || ((HVK_HALO_ABL & 2) && acc[0][j][0] != 1234.5f)) continue;
     const int tl = jg / NP, pl_ = jg - (jg / NP) * NP;
     const int khg = kh0 + tl / KW, kwl = tl - (tl / KW) * KW;
-    const int ng = (khg * g.KW + kwl) * g.Cg + cc * 16 * NP + pl_ * 16 + fq * 4;
+    const int ng = (khg * g.KW + kwl) * g.Cg + cc * 16 * NP + pl_ * 16 + fqe * 4;
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
-      const int mg = coff_y + mrow0 + i * 16 + fr;
+      const int mg = coff_y + mrow0 + i * 16 + fre;
       *(float4*)(ws + (sbase + mg) * g.KK + ng) =
           make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
     }
   }
-  if (bwave && fq == 0) {
+  if (bwave && fqe == 0) {
 #pragma unroll
     for (int i = 0; i < MI; ++i)
-      wsb[sbase + coff_y + mrow0 + i * 16 + fr] = accb[i][0];
+      wsb[sbase + coff_y + mrow0 + i * 16 + fre] = accb[i][0];
   }
 }
 
@@ -1056,6 +1217,9 @@ int g_halo_pad = 2;
 // the bf16 kernel's lean pixel loop (hvk_halo_lean; 0: the old loop, for
 // A/B runs and the bitwise tests)
 int g_halo_lean = 1;
+// the lean loop with one LDS object per stage (hvk_halo_stages; 0: both
+// stages in one array, for A/B runs and the bitwise tests)
+int g_halo_stages = 1;
 
 // fp8: 1-byte elements, 128-pixel steps, 16-B slots (Wp = OW + 16) and the
 // fp8 candidate list
@@ -1175,24 +1339,35 @@ HVK_API long long hvk_conv_wgrad_halo(const void* X, const void* dY, float* dW,
   const int bias = dbias != nullptr;
   const uint16_t* x = (const uint16_t*)X;
   const uint16_t* dy = (const uint16_t*)dY;
-#define HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, LEAN)                          \
+#define HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, LEAN, STG)                     \
   hipLaunchKernelGGL(                                                          \
-      (wgrad_halo_kernel<MT, NP, KHT, KW, NJW, PB, SEG, LEAN>), grid, blk, 0,  \
-      s, x, dy, ws, wsb, p.g, p.mtiles, p.cchunks, p.kgroups, p.tiles,         \
-      p.kspan, bias)
+      (wgrad_halo_kernel<MT, NP, KHT, KW, NJW, PB, SEG, LEAN, STG>), grid,     \
+      blk, 0, s, x, dy, ws, wsb, p.g, p.mtiles, p.cchunks, p.kgroups,          \
+      p.tiles, p.kspan, bias)
 #define HALO_GO(MT, NP, KHT, KW, NJW, PB, SEG)                                 \
-  if (g_halo_lean) HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, true);              \
-  else HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, false)
+  if (g_halo_lean && g_halo_stages)                                            \
+    HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, true, true);                       \
+  else if (g_halo_lean) HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, true, false);  \
+  else HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, false, false)
+#define HALO_GO_ONE(MT, NP, KHT, KW, NJW, PB, SEG)                             \
+  if (g_halo_lean) HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, true, false);       \
+  else HALO_GO1(MT, NP, KHT, KW, NJW, PB, SEG, false, false)
   switch (p.var) {
+    // the two-object stages where they measured faster (AlexNet conv1,
+    // conv3-5).  On the one-array loop: conv2's 5 x 5 form (measured 2 %
+    // slower with them), the VGG 56 / 112 segment form (three registers
+    // short: it spills, one reload in the loop), and the VGG 28 and 224
+    // wide forms (listings clean, not measured yet) - docs/OPS.md
     case 1: HALO_GO(128, 2, 3, 3, 9, 7168, false); break;
     case 2: HALO_GO(96, 2, 3, 3, 9, 7168, false); break;
-    case 3: HALO_GO(128, 3, 1, 5, 8, 5120, false); break;
-    case 4: HALO_GO(128, 2, 3, 3, 9, 10240, false); break;
-    case 5: HALO_GO(128, 2, 3, 3, 9, 7168, true); break;
-    case 6: HALO_GO(64, 4, 3, 3, 18, 7168, true); break;
+    case 3: HALO_GO_ONE(128, 3, 1, 5, 8, 5120, false); break;
+    case 4: HALO_GO_ONE(128, 2, 3, 3, 9, 10240, false); break;
+    case 5: HALO_GO_ONE(128, 2, 3, 3, 9, 7168, true); break;
+    case 6: HALO_GO_ONE(64, 4, 3, 3, 18, 7168, true); break;
     case 7: HALO_GO(96, 3, 3, 3, 14, 8192, true); break;
     default: return -1;
   }
+#undef HALO_GO_ONE
 #undef HALO_GO
 #undef HALO_GO1
   hipError_t e = launch_status(s);
@@ -1222,6 +1397,10 @@ HVK_API void hvk_halo_pitch_pad(int p) { g_halo_pad = p; }
 // lean pixel loop of the bf16 halo kernel (1 default; 0: the old loop,
 // bit-identical results)
 HVK_API void hvk_halo_lean(int on) { g_halo_lean = on; }
+
+// one LDS object per stage in the lean loop (1 default; 0: one array and a
+// run-time stage offset, bit-identical results)
+HVK_API void hvk_halo_stages(int on) { g_halo_stages = on; }
 
 // the plan's split count (tests / autotune logging)
 HVK_API int hvk_conv_wgrad_halo_splits(int N, int H, int W, int C, int OC,

@@ -9,7 +9,10 @@ rules 24-25), reporting the median TF/s per setting.
 With a fourth argument ``lean`` the pair is the halo kernel's lean pixel
 loop against its old loop (ops.set_halo_wgrad_lean(True / False)) instead:
 per layer the median and minimum time of each, and for the layer sum the
-old loop's own round-to-round spread next to the difference.
+old loop's own round-to-round spread next to the difference.  With
+``stages`` the pair is the lean loop with one LDS array per stage against the
+lean loop with both stages in one array (ops.set_halo_wgrad_stages), reported
+the same way ("old" is then the one-array loop).
 
 Writes gpurun_out/bench_wgrad_ab.json."""
 import json
@@ -53,7 +56,7 @@ def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     VB = int(sys.argv[3]) if len(sys.argv) > 3 else 0
-    lean = len(sys.argv) > 4 and sys.argv[4] == "lean"
+    lean = len(sys.argv) > 4 and sys.argv[4] in ("lean", "stages")
     cases = [("alex_conv1", (B, 227, 227, 3, 96, 11, 0, 1, 4)),
              ("alex_conv2", (B, 27, 27, 96, 256, 5, 2, 2)),
              ("alex_conv3", (B, 13, 13, 256, 384, 3, 1, 1)),
@@ -67,7 +70,9 @@ def main():
                   ("vgg_conv5_2", (VB, 14, 14, 512, 512, 3, 1, 1))]
     out = {}
     if lean:   # the lean / old pair instead; the same output file
-        out, cases = main_lean(cases, rounds), []
+        setter = (ops.set_halo_wgrad_lean if sys.argv[4] == "lean"
+                  else ops.set_halo_wgrad_stages)
+        out, cases = main_lean(cases, rounds, setter, sys.argv[4]), []
     for name, shp in cases:
         fl, fn = case(*shp)
         res = {"halo": [], "gemm": []}
@@ -88,8 +93,8 @@ def main():
         json.dump(out, f, indent=1)
 
 
-def main_lean(cases, rounds):
-    """old / lean alternating round by round; times in microseconds"""
+def main_lean(cases, rounds, setter, new):
+    """old / new loop alternating round by round; times in microseconds"""
     out = {}
     sums = {"old": [0.0] * rounds, "lean": [0.0] * rounds}
     for name, shp in cases:
@@ -99,23 +104,23 @@ def main_lean(cases, rounds):
             # one untimed round of both: the first timing of a layer (cold
             # caches and clocks) would otherwise always be the old loop's
             for on in (False, True):
-                ops.set_halo_wgrad_lean(on)
+                setter(on)
                 timeit(fn)
             for r in range(rounds):
                 for key, on in (("old", False), ("lean", True)):
-                    ops.set_halo_wgrad_lean(on)
+                    setter(on)
                     t = timeit(fn) * 1e6
                     res[key].append(t)
                     sums[key][r] += t
         finally:
-            ops.set_halo_wgrad_lean(True)
+            setter(True)
         st = {k: {"median": statistics.median(v), "min": min(v)}
               for k, v in res.items()}
         out[name] = {"shape": shp, "us": st, "runs": res,
                      "tflops_median": {k: fl / st[k]["median"] / 1e6
                                        for k in st}}
-        print("%-12s old %8.1f us (min %8.1f)  lean %8.1f us (min %8.1f)  "
-              "%+.1f %%" % (name, st["old"]["median"], st["old"]["min"],
+        print("%-12s old %8.1f us (min %8.1f)  %s %8.1f us (min %8.1f)  "
+              "%+.1f %%" % (name, st["old"]["median"], st["old"]["min"], new,
                             st["lean"]["median"], st["lean"]["min"],
                             (st["old"]["median"] / st["lean"]["median"] - 1)
                             * 100), flush=True)
@@ -124,8 +129,8 @@ def main_lean(cases, rounds):
     med = {k: statistics.median(v) for k, v in sums.items()}
     spread = max(sums["old"]) - min(sums["old"])
     out["sum"] = {"runs": sums, "median": med, "old_spread": spread}
-    print("sum          old %8.1f us  lean %8.1f us  gain %.1f us, the old "
-          "loop's own spread %.1f us" % (med["old"], med["lean"],
+    print("sum          old %8.1f us  %s %8.1f us  gain %.1f us, the old "
+          "loop's own spread %.1f us" % (med["old"], new, med["lean"],
                                          med["old"] - med["lean"], spread))
     return out
 

@@ -1282,6 +1282,15 @@ def set_halo_wgrad_lean(on):
         _lib.lib().hvk_halo_lean(int(bool(on)))
 
 
+def set_halo_wgrad_stages(on):
+    """A/B knob of the lean loop's LDS stages (default on: one LDS object
+    per stage, so that the next step's DMA stays in flight under this
+    step's fragment reads and MFMAs); off is the lean loop with both stages
+    in one array.  Results are bit-identical."""
+    if _lib.available():
+        _lib.lib().hvk_halo_stages(int(bool(on)))
+
+
 def _halo_wgrad(x, dy, dw, dbias, N, H, W, C, OC, KH, KW, pt, pl, OH, OW,
                 groups, splits=None):
     """Stride-1 weight gradient on the halo kernel (csrc/kernels/

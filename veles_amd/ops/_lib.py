@@ -134,6 +134,7 @@ _SIGS = {
 _OPTIONAL = {
     "hvk_hc32_handover": [I],
     "hvk_halo_lean": [I],
+    "hvk_halo_stages": [I],
     "hvk_hc_max_wgs": [I],
     # only in the -DHVK_HC_ABL build (tools/build_abl.py hc)
     "hvk_hc_stamps": [P],
