@@ -46,6 +46,23 @@ int hvk_bn_bwd(const void* x, long long ldx, const void* err, long long lde,
                const float* gamma, const float* mean, const float* invstd,
                float* dgamma, float* dbeta, int accumulate, int act,
                int aux_act, float* coef, float* ws, hipStream_t s);
+// layer normalisation and the residual add (layernorm.hip): bf16 [P][C] with
+// row pitches in elements, r null: no residual; ws: 2 * C * hvk_ln_partials
+int hvk_ln_partials(long long P, int C, int vec);
+int hvk_ln_vec(const void* x, long long ldx, int C);
+int hvk_ln_colsum(int mode);
+int hvk_ln_fwd(const void* x, long long ldx, const void* r, long long ldr,
+               void* y, long long ldy, long long P, int C, const float* gamma,
+               const float* beta, float eps, float* mean, float* invstd,
+               hipStream_t s);
+int hvk_ln_bwd(const void* err, long long lde, const void* x, long long ldx,
+               const void* r, long long ldr, void* dx, long long lddx,
+               long long P, int C, int vec, const float* gamma,
+               const float* mean, const float* invstd, float* dgamma,
+               float* dbeta, int accumulate, int need_dx, float* ws,
+               hipStream_t s);
+int hvk_add(const void* a, long long lda, const void* b, long long ldb,
+            void* out, long long ldo, long long P, int C, hipStream_t s);
 // self-attention (attention.hip): bf16 [B][T][NH*D] views with row pitches,
 // float32 lse / delta [B][NH][T]; D = 32, 64 or 128
 int hvk_attn_tile(int which);

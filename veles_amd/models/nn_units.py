@@ -71,6 +71,13 @@ def _sync_device(t):
         import torch
         torch.cuda.synchronize(t.device)
 
+def _compute_dtype(t):
+    """The dtype the streaming layers work in on ``t``'s device: bf16 on the
+    GPU, float32 on the CPU path"""
+    import torch
+    return torch.bfloat16 if t.is_cuda else torch.float32
+
+
 class Forward(AcceleratedUnit):
     """Base forward layer."""
     hide_from_registry = True

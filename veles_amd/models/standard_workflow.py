@@ -40,6 +40,7 @@ from veles_amd.models.gd import (
 from veles_amd.models.gd_conv import (
     GDRELUConv, GDSigmoidConv, GDStrictRELUConv, GDTanhConv,
     GradientDescentConv)
+from veles_amd.models.layer_norm import GDLayerNorm, LayerNorm
 from veles_amd.models.lr_adjust import LearningRateAdjust
 from veles_amd.models.normalization_units import (
     LRNormalizerBackward, LRNormalizerForward)
@@ -54,6 +55,7 @@ from veles_amd.models.cutter import Cutter, GDCutter
 from veles_amd.models.deconv import Deconv, GDDeconv
 from veles_amd.models.recurrent import (
     GDGRU, GDLSTM, GDRNN, GRU, LSTM, RNN)
+from veles_amd.models.residual import GDResidual, GDSkip, Residual, Skip
 from veles_amd.models.rprop_all2all import RPropAll2All
 from veles_amd.models.standard_workflow_links import LinkBuilders
 from veles_amd.models.weights_zerofilling import GDZeroFiller, ZeroFiller
@@ -95,6 +97,9 @@ LAYER_TYPES = {
     "rnn": (RNN, GDRNN),
     "gru": (GRU, GDGRU),
     "attention": (Attention, GDAttention),
+    "layer_norm": (LayerNorm, GDLayerNorm),
+    "skip": (Skip, GDSkip),
+    "residual": (Residual, GDResidual),
     "norm": (LRNormalizerForward, LRNormalizerBackward),
     "batch_norm": (bn_units.BatchNorm, bn_units.GDBatchNorm),
     "batch_norm_tanh": (bn_units.BatchNormTanh, bn_units.GDBatchNormTanh),
@@ -326,10 +331,35 @@ class StandardWorkflow(LinkBuilders, AcceleratedWorkflow):
             if getattr(unit, "has_weights", False) and \
                     hasattr(unit, "register_params"):
                 weighted = unit
+            if isinstance(unit, Residual) and unit.residual is None:
+                raise ValueError("%s: a residual layer names its skip layer "
+                                 "(residual=\"<name>\")" % name)
+            if getattr(unit, "residual", None) is not None:
+                self._link_skip(unit)
             self.forwards.append(unit)
             prev = unit
             del allowed
+        for unit in self.forwards:
+            if isinstance(unit, Skip) and not unit.consumers:
+                raise ValueError("skip layer %s: no later layer adds it back "
+                                 "(residual=%r)" % (unit.name, unit.name))
         return prev
+
+    def _link_skip(self, unit):
+        """``residual="n"``: n is the name of an EARLIER layer, a skip"""
+        want = unit.residual
+        found = [f for f in self.forwards if f.name == want]
+        if not found:
+            later = any(l.get("name", "%s%d" % (l["type"], i)) == want
+                        for i, l in enumerate(self.layers))
+            raise ValueError("%s: residual=%r names %s" % (
+                unit.name, want, "a later layer (or itself)" if later
+                else "no layer"))
+        if not isinstance(found[-1], Skip):
+            raise ValueError("%s: residual=%r names %s, which is not a skip "
+                             "layer" % (unit.name, want, found[-1].name))
+        unit.skip_unit = found[-1]
+        found[-1].consumers.append(unit)
 
     @staticmethod
     def _filter(cls, kw):
@@ -419,6 +449,14 @@ class StandardWorkflow(LinkBuilders, AcceleratedWorkflow):
             gds[i] = gd
             prev = gd
         gds[0].need_err_input = False
+        # a skip's gradient fan-in: its consumers' GD units, in layer order
+        # (every one of them runs before the GDSkip does).  Their err_input
+        # doubles as the skip gradient, so no derivative of the layer below
+        # is fused into it: none of these classes is in _FUSABLE
+        for i, fwd in enumerate(self.forwards):
+            if isinstance(fwd, Skip):
+                gds[i].consumer_gds = [gds[self.forwards.index(c)]
+                                       for c in fwd.consumers]
         # fold the activation derivative of layer i-1 into gds[i]
         for i in range(1, n):
             below = self.forwards[i - 1]

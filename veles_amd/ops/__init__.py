@@ -34,7 +34,8 @@ __all__ = ["ACT", "gemm", "linear_fwd", "conv_out_size", "conv_fwd",
            "kohonen_argmin", "kohonen_update", "lstm_fwd", "lstm_bwd",
            "rbm_layout", "rbm_uniforms", "rbm_sample", "rbm_grad",
            "bn_partials", "batchnorm_fwd", "batchnorm_bwd", "attention_fwd",
-           "attention_bwd", "mha_fwd", "mha_bwd", "attn_head_dim"]
+           "attention_bwd", "mha_fwd", "mha_bwd", "attn_head_dim",
+           "ln_partials", "layernorm_fwd", "layernorm_bwd", "add"]
 
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2, torch.int32: 3,
       torch.float16: 4}
@@ -2004,6 +2005,167 @@ def batchnorm_bwd(err, x, y, gamma, save, dgamma, dbeta, act=0,
     if aux_act:
         dx = dx * act_bwd_ref(aux.reshape(P, C), aux_act)
     out.copy_(dx.view(out.shape))
+    return out
+
+
+# ------------------------------- layer normalisation, residual connections
+LN_CPU_CHAIN = 16     # CPU path: float32 sums of 16 columns, level by level
+
+
+def ln_partials(P, C, vec):
+    """Slices per column of the column sums (dgamma, dbeta) of
+    ``hvk_ln_bwd`` over [P][C]: a function of the shape and the path
+    (``vec``: 8 columns per lane) only, never of the device."""
+    g = _bn_fn("hvk_ln_partials")(int(P), int(C), int(bool(vec)))
+    if g < 1:
+        raise ValueError("layernorm: no grid for P = %d, C = %d, vec = %s" %
+                         (P, C, vec))
+    return g
+
+
+def _ln_row_sum(t):
+    """[P][C] float32 -> [P]: sums of LN_CPU_CHAIN neighbours, level by
+    level (no float32 chain is longer than LN_CPU_CHAIN per level)"""
+    while t.shape[1] > 1:
+        pad = -t.shape[1] % LN_CPU_CHAIN
+        if pad:
+            t = F.pad(t, (0, pad))
+        t = t.reshape(t.shape[0], -1, LN_CPU_CHAIN).sum(2)
+    return t[:, 0]
+
+
+def _ln_vec(C, *pairs):
+    fn = _bn_fn("hvk_ln_vec")
+    return C % 8 == 0 and all(
+        t is None or fn(_p(t), int(ld), C) for t, ld in pairs)
+
+
+def layernorm_fwd(x, gamma, beta, *, residual=None, eps=1e-5, save=None,
+                  out=None):
+    """Layer normalisation over the last axis of ``x`` (every other axis is
+    a row): ``torch.nn.LayerNorm(C, eps)`` of s = x (+ ``residual``):
+    y = gamma (s - mean) invstd + beta with each row's mean and biased
+    variance, in training and evaluation alike.  ``save`` gets ``mean`` and
+    ``invstd`` (float32 [P]).  s is not stored: with a residual it is
+    float(x) + float(residual) in float32, never rounded, and
+    ``layernorm_bwd`` adds the two again.
+
+    GPU: bf16 ``x`` / ``residual`` / ``out``, float32 everything else
+    (``hvk_ln_fwd``, one launch).  CPU: float32 throughout.  A caller that
+    keeps ``save`` (a dict) gets the same buffers at every call."""
+    name = "layernorm_fwd"
+    P, C, ldx = _bn_rows(name, "x", x)
+    _bn_xdtype(name, x)
+    _bn_vecs(name, C, x, gamma=gamma, beta=beta)
+    ldr = C
+    if residual is not None:
+        _, _, ldr = _bn_rows(name, "residual", residual, like=x)
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    _, _, ldy = _bn_rows(name, "out", out, like=x)
+    save = {} if save is None else save
+    dev = x.device
+    mean = _rec_buf(save, "mean", (P,), torch.float32, dev)
+    invstd = _rec_buf(save, "invstd", (P,), torch.float32, dev)
+    if _gpu(x):
+        _lib.check(_bn_fn("hvk_ln_fwd")(
+            _p(x), ldx, _p(residual), ldr, _p(out), ldy, P, C, _p(gamma),
+            _p(beta), float(eps), _p(mean), _p(invstd), _s(x)), "hvk_ln_fwd")
+        return out
+    s = x.reshape(P, C)
+    if residual is not None:
+        s = s + residual.reshape(P, C)
+    m = _ln_row_sum(s) / C
+    d = s - m[:, None]
+    var = _ln_row_sum(d * d) / C
+    mean.copy_(m)
+    invstd.copy_(1.0 / torch.sqrt(var + eps))
+    out.copy_(((d * invstd[:, None]) * gamma + beta).view(out.shape))
+    return out
+
+
+def layernorm_bwd(err, x, gamma, save, dgamma, dbeta, *, residual=None,
+                  accumulate="overwrite", out=None, ws=None, need_dx=True):
+    """Backward of ``layernorm_fwd``.  With sh = (s - mean) invstd and gh =
+    err gamma: dbeta = sum_P err, dgamma = sum_P err sh, written
+    (``"overwrite"``) or added (True) to ``dbeta`` / ``dgamma``; returns
+    ds = invstd (gh - mean_C(gh) - sh mean_C(gh sh)) (None with ``need_dx``
+    False), which is the gradient of x and of the residual alike.  ``save``
+    is the forward's.  GPU: ``hvk_ln_bwd`` (the dx / column-partials launch
+    or launches, then the finish); CPU: float32."""
+    name = "layernorm_bwd"
+    P, C, ldx = _bn_rows(name, "x", x)
+    _bn_xdtype(name, x)
+    _, _, lde = _bn_rows(name, "err", err, like=x)
+    if accumulate not in (True, "overwrite"):
+        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
+                         name)
+    ldr = lddx = C
+    if residual is not None:
+        _, _, ldr = _bn_rows(name, "residual", residual, like=x)
+    _bn_vecs(name, C, x, gamma=gamma, dgamma=dgamma, dbeta=dbeta)
+    dev = x.device
+    _rec_save_check(name, "layernorm_fwd", save,
+                    (("mean", (P,), torch.float32),
+                     ("invstd", (P,), torch.float32)), dev)
+    if need_dx:
+        if out is None:
+            out = torch.empty(x.shape, dtype=x.dtype, device=dev)
+        _, _, lddx = _bn_rows(name, "out", out, like=x)
+    else:
+        out = None
+    ws = {} if ws is None else ws
+    mean, invstd = save["mean"], save["invstd"]
+    if _gpu(x):
+        vec = _ln_vec(C, (err, lde), (x, ldx), (residual, ldr), (out, lddx),
+                      (gamma, 8))
+        G = ln_partials(P, C, vec)
+        w = _rec_buf(ws, "bwd", (2 * C * G,), torch.float32, dev)
+        _lib.check(_bn_fn("hvk_ln_bwd")(
+            _p(err), lde, _p(x), ldx, _p(residual), ldr, _p(out), lddx, P, C,
+            int(vec), _p(gamma), _p(mean), _p(invstd), _p(dgamma),
+            _p(dbeta), int(accumulate is True), int(bool(need_dx)), _p(w),
+            _s(x)), "hvk_ln_bwd")
+        return out
+    s = x.reshape(P, C)
+    if residual is not None:
+        s = s + residual.reshape(P, C)
+    g = err.reshape(P, C)
+    sh = (s - mean[:, None]) * invstd[:, None]
+    db = _bn_chain_sum(g)
+    dg = _bn_chain_sum(g * sh)
+    if accumulate is True:
+        dbeta.add_(db)
+        dgamma.add_(dg)
+    else:
+        dbeta.copy_(db)
+        dgamma.copy_(dg)
+    if out is None:
+        return None
+    gh = g * gamma
+    c1 = _ln_row_sum(gh) / C
+    c2 = _ln_row_sum(gh * sh) / C
+    out.copy_((invstd[:, None] * (gh - c1[:, None] - sh * c2[:, None]))
+              .view(out.shape))
+    return out
+
+
+def add(a, b, out=None):
+    """out = a + b over tensors of one shape whose last axis has contiguous
+    elements (the residual add and the gradient fan-in).  GPU: bf16,
+    ``hvk_add``: bf16(float(a) + float(b)); CPU: float32."""
+    name = "add"
+    P, C, lda = _bn_rows(name, "a", a)
+    _bn_xdtype(name, a)
+    _, _, ldb = _bn_rows(name, "b", b, like=a)
+    if out is None:
+        out = torch.empty(a.shape, dtype=a.dtype, device=a.device)
+    _, _, ldo = _bn_rows(name, "out", out, like=a)
+    if _gpu(a):
+        _lib.check(_bn_fn("hvk_add")(
+            _p(a), lda, _p(b), ldb, _p(out), ldo, P, C, _s(a)), "hvk_add")
+        return out
+    torch.add(a, b, out=out)
     return out
 
 

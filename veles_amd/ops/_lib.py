@@ -195,6 +195,17 @@ _OPTIONAL = {
     "hvk_attn_bwd_delta": [P, L] * 2 + [P, I, I, I, I, P],
     "hvk_attn_bwd_dkv": [P, L] * 4 + [P, P] + [P, L] * 2 + [I, I, I, I, I, P],
     "hvk_attn_bwd_dq": [P, L] * 4 + [P, P] + [P, L] + [I, I, I, I, I, P],
+    # layer normalisation and the residual add (csrc/kernels/layernorm.hip):
+    # (P, C, vec); (x, ldx, C); (mode); (x, r, y each with its pitch, P, C,
+    # gamma, beta, eps, mean, invstd, s); (err, x, r, dx each with its pitch,
+    # P, C, vec, gamma, mean, invstd, dgamma, dbeta, accumulate, need_dx, ws,
+    # s); (a, b, out each with its pitch, P, C, s)
+    "hvk_ln_partials": [L, I, I],
+    "hvk_ln_vec": [P, L, I],
+    "hvk_ln_colsum": [I],
+    "hvk_ln_fwd": [P, L] * 3 + [L, I, P, P, F, P, P, P],
+    "hvk_ln_bwd": [P, L] * 4 + [L, I, I, P, P, P, P, P, I, I, P, P],
+    "hvk_add": [P, L] * 3 + [L, I, P],
 }
 # functions returning a pointer / a 64-bit int (every other one returns int)
 _PTR_RET = {"hvk_stream_create"}
