@@ -63,6 +63,16 @@ int hvk_ln_bwd(const void* err, long long lde, const void* x, long long ldx,
                hipStream_t s);
 int hvk_add(const void* a, long long lda, const void* b, long long ldb,
             void* out, long long ldo, long long P, int C, hipStream_t s);
+// feed-forward activation passes (ffn.hip): bf16 [P][F] with row pitches in
+// elements; act 0 gelu, 1 gelu_tanh, 2 strict relu; dut null: no du^T; ws:
+// F * hvk_ffn_act_partials(P, F, dut != null) floats
+int hvk_ffn_act_partials(long long P, int F, int transposed);
+int hvk_ffn_act_fwd(const void* u, long long ldu, void* h, long long ldh,
+                    long long P, int F, int act, hipStream_t s);
+int hvk_ffn_act_bwd(const void* dh, long long lddh, const void* u,
+                    long long ldu, void* du, long long lddu, void* dut,
+                    long long lddut, long long P, int F, int act, float* db1,
+                    int accumulate, float* ws, hipStream_t s);
 // self-attention (attention.hip): bf16 [B][T][NH*D] views with row pitches,
 // float32 lse / delta [B][NH][T]; D = 32, 64 or 128
 int hvk_attn_tile(int which);

@@ -12,6 +12,12 @@ and 64-bit multiply-adds), SALU, branches, waits, LDS and buffer loads.
 ``saveexec`` counts the exec-masked regions opened in the loop.  The counts
 are static (an inner scalar loop counts once).  Needs no GPU.
 
+    python tools/isa_loop_mix.py --any ffn.s [substring]
+
+takes the innermost loops with vector memory accesses instead, for kernels
+without MFMAs (the element-wise passes: VALU per element = valu / the
+elements a lane handles per turn).
+
     python tools/isa_loop_mix.py --waits wgrad_halo.s [substring]
 
 reports instead, per loop, the ``s_waitcnt vmcnt`` instructions that stand
@@ -94,7 +100,9 @@ def kernels(path):
     return [(n, vg.get(n), body) for n, body in out]
 
 
-def mfma_loops(body):
+def mfma_loops(body, any_loop=False):
+    """the outermost loops that hold MFMAs; ``any_loop``: the INNERMOST loops
+    with vector memory accesses instead (element-wise kernels)"""
     pos = {lab: i for i, (lab, _, _) in enumerate(body) if lab}
     loops = []
     for i, (lab, op, args) in enumerate(body):
@@ -102,8 +110,13 @@ def mfma_loops(body):
             tgt = args.strip()
             if tgt in pos and pos[tgt] < i:
                 seg = body[pos[tgt]:i + 1]
-                if any(o and o.startswith("v_mfma") for _, o, _ in seg):
+                want = ("global_", "buffer_") if any_loop else ("v_mfma",)
+                if any(o and o.startswith(want) for _, o, _ in seg):
                     loops.append((pos[tgt], i))
+    if any_loop:
+        return [l for l in loops
+                if not any(o != l and l[0] <= o[0] and o[1] <= l[1]
+                           for o in loops)]
     # outermost only
     return [l for l in loops
             if not any(o != l and o[0] <= l[0] and l[1] <= o[1]
@@ -193,6 +206,9 @@ def main():
     if sys.argv[1] == "--waits":
         return main_waits(sys.argv[2], sys.argv[3] if len(sys.argv) > 3
                           else "")
+    any_loop = sys.argv[1] == "--any"
+    if any_loop:
+        del sys.argv[1]
     path = sys.argv[1]
     sub = sys.argv[2] if len(sys.argv) > 2 else ""
     print("| kernel | loop | " + " | ".join(COLS) + " | VGPRs |")
@@ -200,7 +216,7 @@ def main():
     for name, vgprs, body in kernels(path):
         if sub not in name:
             continue
-        for k, (a, b) in enumerate(mfma_loops(body)):
+        for k, (a, b) in enumerate(mfma_loops(body, any_loop)):
             c = mix(body[a:b + 1])
             print("| %s | %d | %s | %s |" % (
                 name, k, " | ".join(str(c[x]) for x in COLS), vgprs))

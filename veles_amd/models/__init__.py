@@ -6,6 +6,7 @@ from veles_amd.models.gd_conv import *  # noqa: F401,F403
 from veles_amd.models.pooling import *  # noqa: F401,F403
 from veles_amd.models.normalization_units import *  # noqa: F401,F403
 from veles_amd.models.batch_norm import *  # noqa: F401,F403
+from veles_amd.models.feed_forward import *  # noqa: F401,F403
 from veles_amd.models.layer_norm import *  # noqa: F401,F403
 from veles_amd.models.residual import *  # noqa: F401,F403
 from veles_amd.models.dropout import *  # noqa: F401,F403

@@ -35,6 +35,7 @@ from veles_amd.models.conv import (
 from veles_amd.models.decision import DecisionGD, DecisionMSE
 from veles_amd.models.dropout import DropoutBackward, DropoutForward
 from veles_amd.models.evaluator import EvaluatorMSE, EvaluatorSoftmax
+from veles_amd.models.feed_forward import FeedForward, GDFeedForward
 from veles_amd.models.gd import (
     GDRELU, GDSigmoid, GDSoftmax, GDStrictRELU, GDTanh, GradientDescent)
 from veles_amd.models.gd_conv import (
@@ -97,6 +98,7 @@ LAYER_TYPES = {
     "rnn": (RNN, GDRNN),
     "gru": (GRU, GDGRU),
     "attention": (Attention, GDAttention),
+    "ffn": (FeedForward, GDFeedForward),
     "layer_norm": (LayerNorm, GDLayerNorm),
     "skip": (Skip, GDSkip),
     "residual": (Residual, GDResidual),
@@ -125,7 +127,8 @@ LAYER_TYPES = {
 # GD classes whose err_input kernel can multiply by f'(aux) in its epilogue
 _FUSABLE = (GradientDescent, GradientDescentConv, GDMaxPooling, GDAvgPooling,
             GDMaxAbsPooling, LRNormalizerBackward, DropoutBackward,
-            act_units.ActivationBackward, bn_units.GDBatchNorm, GDAttention)
+            act_units.ActivationBackward, bn_units.GDBatchNorm, GDAttention,
+            GDFeedForward)
 _POOL_KW = ("kx", "ky", "sliding")
 _LRN_KW = ("alpha", "beta", "k", "n")
 

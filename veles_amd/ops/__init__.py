@@ -35,7 +35,9 @@ __all__ = ["ACT", "gemm", "linear_fwd", "conv_out_size", "conv_fwd",
            "rbm_layout", "rbm_uniforms", "rbm_sample", "rbm_grad",
            "bn_partials", "batchnorm_fwd", "batchnorm_bwd", "attention_fwd",
            "attention_bwd", "mha_fwd", "mha_bwd", "attn_head_dim",
-           "ln_partials", "layernorm_fwd", "layernorm_bwd", "add"]
+           "ln_partials", "layernorm_fwd", "layernorm_bwd", "add",
+           "FFN_ACT", "ffn_partials", "ffn_act_fwd", "ffn_act_bwd",
+           "ffn_fwd", "ffn_bwd", "set_ffn_tile"]
 
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2, torch.int32: 3,
       torch.float16: 4}
@@ -4437,4 +4439,319 @@ def mha_bwd(err, x, w_in, w_out, save, dw_in, dw_out, dbias, heads, *,
         err_input = torch.empty(B, T, I, dtype=dt, device=dev)
     gemm(dqkv, wi, out=err_input.view(B * T, I),
          aux=aux.reshape(B * T, I) if aux_act else None, aux_act=aux_act)
+    return err_input
+
+
+# ------------------------------------------------ position-wise feed-forward
+FFN_ACT = {"gelu": 0, "gelu_tanh": 1, "str": 2}
+_FFN_C = 0.7978845608028654       # sqrt(2 / pi)
+_FFN_K = 0.044715
+
+# du^T of ffn_bwd's NN weight gradient: True, the tile path of
+# hvk_ffn_act_bwd (one pass, 8 B per element); False, the plain backward and
+# then transpose_colsum (10 B per element).  Same bits either way; a
+# measuring switch for tools/bench_ffn.py and the tests.
+_FFN_TILE = True
+
+
+def set_ffn_tile(on):
+    """Switch ``ffn_bwd``'s du^T between the tile path (True, the default)
+    and plain backward + ``transpose_colsum``; returns the old value."""
+    global _FFN_TILE
+    old, _FFN_TILE = _FFN_TILE, bool(on)
+    return old
+
+
+def ffn_act_code(act):
+    try:
+        return FFN_ACT[act]
+    except (KeyError, TypeError):
+        raise ValueError("ffn: unknown activation %r (one of %s)" % (
+            act, ", ".join(sorted(FFN_ACT)))) from None
+
+
+def ffn_partials(P, F, transposed):
+    """Slabs per column of ``hvk_ffn_act_bwd``'s column sums over [P][F]: a
+    function of the shape and of whether du^T is written only."""
+    g = _bn_fn("hvk_ffn_act_partials")(int(P), int(F), int(bool(transposed)))
+    if g < 1:
+        raise ValueError("ffn: no grid for P = %d, F = %d, transposed = %s" %
+                         (P, F, transposed))
+    return g
+
+
+def ffn_act_ref(u, act):
+    """a(u) in ``u``'s own floating-point type (the CPU path, float32)"""
+    code = ffn_act_code(act)
+    if code == 0:
+        return 0.5 * u * (1.0 + torch.erf(u * (0.5 ** 0.5)))
+    if code == 1:
+        return 0.5 * u * (1.0 + torch.tanh(
+            _FFN_C * (u + _FFN_K * u * u * u)))
+    return torch.where(u > 0, u, torch.zeros_like(u))
+
+
+def ffn_dact_ref(u, act):
+    """a'(u), from the pre-activation"""
+    code = ffn_act_code(act)
+    if code == 0:
+        return 0.5 * (1.0 + torch.erf(u * (0.5 ** 0.5))) + \
+            u * torch.exp(-0.5 * u * u) * 0.3989422804014327
+    if code == 1:
+        t = torch.tanh(_FFN_C * (u + _FFN_K * u * u * u))
+        return 0.5 * (1.0 + t) + 0.5 * u * (1.0 - t * t) * \
+            (_FFN_C * (1.0 + 3.0 * _FFN_K * u * u))
+    return (u > 0).to(u.dtype)
+
+
+def ffn_act_fwd(u, act="gelu", out=None):
+    """h = a(u) over a tensor whose last axis has contiguous elements (any
+    contiguous shape, or 2-D rows with a pitch).  ``out`` may be ``u``.
+    GPU: bf16, ``hvk_ffn_act_fwd`` (float32 inside); CPU: float32."""
+    name = "ffn_act_fwd"
+    code = ffn_act_code(act)
+    P, F_, ldu = _bn_rows(name, "u", u)
+    _bn_xdtype(name, u)
+    if out is None:
+        out = torch.empty(u.shape, dtype=u.dtype, device=u.device)
+    _, _, ldh = _bn_rows(name, "out", out, like=u)
+    if _gpu(u):
+        _lib.check(_bn_fn("hvk_ffn_act_fwd")(
+            _p(u), ldu, _p(out), ldh, P, F_, code, _s(u)), "hvk_ffn_act_fwd")
+        return out
+    out.copy_(ffn_act_ref(u, act))
+    return out
+
+
+def ffn_act_bwd(dh, u, act="gelu", *, out=None, out_t=None, db1=None,
+                accumulate="overwrite", ws=None):
+    """du = dh a'(u) (``out``, which may be ``dh``); ``out_t`` [F][P], when
+    given, gets du^T; ``db1`` float32 [F], when given, gets (``"overwrite"``)
+    or is added (True) the column sums of the STORED du.  GPU: bf16,
+    ``hvk_ffn_act_bwd``: one pass plus the ordered finish, the tile path when
+    ``out_t`` is given (P and F multiples of 64); ``ws`` (a dict) keeps the
+    slab workspace.  CPU: float32."""
+    name = "ffn_act_bwd"
+    code = ffn_act_code(act)
+    P, F_, ldu = _bn_rows(name, "u", u)
+    _bn_xdtype(name, u)
+    _, _, lddh = _bn_rows(name, "dh", dh, like=u)
+    if accumulate not in (True, "overwrite"):
+        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
+                         name)
+    if out is None:
+        out = torch.empty(u.shape, dtype=u.dtype, device=u.device)
+    _, _, lddu = _bn_rows(name, "out", out, like=u)
+    if db1 is not None:
+        _bn_vecs(name, F_, u, db1=db1)
+    lddut = P
+    if out_t is not None:
+        if not isinstance(out_t, torch.Tensor) or \
+                tuple(out_t.shape) != (F_, P) or out_t.dtype != u.dtype or \
+                out_t.device != u.device or out_t.stride(1) != 1 or \
+                (F_ > 1 and out_t.stride(0) < P):
+            raise ValueError("%s: out_t must be a %s [%d][%d] with contiguous "
+                             "rows on %s" % (name, u.dtype, F_, P, u.device))
+        lddut = out_t.stride(0) if F_ > 1 else P
+        if _gpu(u) and (P % 64 or F_ % 64):
+            raise ValueError("%s: out_t needs P and F multiples of 64, got "
+                             "%d x %d" % (name, P, F_))
+    if _gpu(u):
+        ws = {} if ws is None else ws
+        G = ffn_partials(P, F_, out_t is not None)
+        w = _rec_buf(ws, "act_bwd", (F_ * G,), torch.float32, u.device)
+        _lib.check(_bn_fn("hvk_ffn_act_bwd")(
+            _p(dh), lddh, _p(u), ldu, _p(out), lddu, _p(out_t), lddut, P, F_,
+            code, _p(db1), int(accumulate is True), _p(w), _s(u)),
+            "hvk_ffn_act_bwd")
+        return out
+    out.copy_(dh * ffn_dact_ref(u, act))
+    if out_t is not None:
+        out_t.copy_(out.reshape(P, F_).t())
+    if db1 is not None:
+        s = _bn_chain_sum(out.reshape(P, F_))
+        if accumulate is True:
+            db1.add_(s)
+        else:
+            db1.copy_(s)
+    return out
+
+
+def _ffn_args(name, x, w1, w2, bias):
+    """Shared host checks of ffn_fwd / ffn_bwd; returns (P, I, F, E, ldx)"""
+    for what, t in (("w1", w1), ("w2", w2)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a tensor, got %s" % (
+                name, what, type(t).__name__))
+    P, I, ldx = _bn_rows(name, "x", x)
+    _bn_xdtype(name, x)
+    if w1.dim() != 2 or w1.shape[1] != I or w1.shape[0] < 1:
+        raise ValueError("%s: w1 must be [F][%d] (I = %d), got %s" % (
+            name, I, I, tuple(w1.shape)))
+    F_ = w1.shape[0]
+    if w2.dim() != 2 or w2.shape[1] != F_ or w2.shape[0] < 1:
+        raise ValueError("%s: w2 must be [E][%d] (F = %d), got %s" % (
+            name, F_, F_, tuple(w2.shape)))
+    E = w2.shape[0]
+    if w1.stride(1) != 1 or w2.stride(1) != 1:
+        raise ValueError("%s: weight rows must be contiguous (strides %s, %s)"
+                         % (name, w1.stride(), w2.stride()))
+    if w1.device != x.device or w2.device != x.device or \
+            (bias is not None and bias.device != x.device):
+        raise ValueError("%s: operands on different devices" % name)
+    if w1.dtype != x.dtype or w2.dtype != x.dtype:
+        raise TypeError("%s: weights must be %s as x, got %s / %s" % (
+            name, x.dtype, w1.dtype, w2.dtype))
+    if bias is not None and (bias.dtype != torch.float32 or
+                             tuple(bias.shape) != (F_ + E,) or
+                             not bias.is_contiguous()):
+        raise ValueError("%s: bias must be a contiguous float32 [%d] = (b1, "
+                         "b2), got %s %s" % (name, F_ + E, bias.dtype,
+                                             tuple(bias.shape)))
+    if P * max(F_, E, ldx) >= 1 << 31:
+        raise ValueError("%s: %d x %d exceeds 2^31 - 1 elements" % (
+            name, P, max(F_, E, ldx)))
+    return P, I, F_, E, ldx
+
+
+def _ffn_wgrad_nn(g, a):
+    """GradientDescent.run's rule for an FC weight gradient g^T a"""
+    from veles_amd.models.gd import _wgrad_nn
+    return _wgrad_nn(g, a)
+
+
+def ffn_fwd(x, w1, w2, bias, act="gelu", *, save=None, out=None, ws=None):
+    """Position-wise feed-forward layer over the last axis of ``x`` (every
+    other axis is a row): float64 ``Sequential(Linear(I, F), GELU(),
+    Linear(F, E))`` is the reference.
+
+        u = x w1^T + bias[:F]      w1 [F][I]
+        h = a(u)                   :func:`ffn_act_fwd`
+        y = h w2^T + bias[F:]      w2 [E][F]
+
+    ``bias`` is [F + E] or None; both biases ride the GEMM epilogues.
+    Returns y, ``x``'s shape with E for I (``out`` when given).  ``save`` (a
+    dict) receives "u" and "h" [P][F] for :func:`ffn_bwd`; without it
+    (evaluation) h overwrites u, which lives in ``ws``.  A kept dict is
+    reused: no allocation from the second call on."""
+    name = "ffn_fwd"
+    ffn_act_code(act)
+    P, I, F_, E, ldx = _ffn_args(name, x, w1, w2, bias)
+    dev, dt = x.device, x.dtype
+    oshape = tuple(x.shape[:-1]) + (E,)
+    if out is not None and (tuple(out.shape) != oshape or
+                            not out.is_contiguous() or out.device != dev or
+                            out.dtype != dt):
+        raise ValueError("%s: out must be a contiguous %s %s on %s" %
+                         (name, dt, oshape, dev))
+    if out is None:
+        out = torch.empty(oshape, dtype=dt, device=dev)
+    st = save if save is not None else (ws if ws is not None else {})
+    u = _rec_buf(st, "u", (P, F_), dt, dev)
+    h = _rec_buf(st, "h", (P, F_), dt, dev) if save is not None else u
+    b1 = None if bias is None else bias[:F_]
+    b2 = None if bias is None else bias[F_:]
+    x2 = x.as_strided((P, I), (ldx, 1))
+    gemm(x2, w1, trans_b=True, bias=b1, out=u)
+    ffn_act_fwd(u, act, out=h)
+    gemm(h, w2, trans_b=True, bias=b2, out=out.view(P, E))
+    return out
+
+
+def ffn_bwd(err, x, w1, w2, save, dw1, dw2, dbias, act="gelu", *,
+            accumulate="overwrite", need_err_input=True, err_input=None,
+            aux=None, aux_act=0):
+    """Backward of :func:`ffn_fwd` from its ``save`` dict; ``err`` is dL/dy.
+
+        dbias[F:] (+)= sum_P err,  dw2 (+)= err^T h,  dh = err w2
+        du = dh a'(u), rounded to the storage type, in dh's buffer
+        dbias[:F] (+)= sum_P du (of the stored du),  dw1 (+)= du^T x
+        err_input = du w1, times f'(aux) of the layer below when ``aux_act``
+        is set (the GEMM's epilogue)
+
+    A weight gradient goes the way ``GradientDescent.run`` sends an FC one:
+    transpose + NN GEMM where its rule allows (err^T and dbias[F:] from
+    ``transpose_colsum``; du^T from the activation kernel's tile path, see
+    :func:`set_ffn_tile`), else the TN GEMM.  ``dw1`` float32 [F][I], ``dw2``
+    float32 [E][F], ``dbias`` float32 [F + E] or None; ``accumulate``: True
+    adds, "overwrite" writes.  ``save`` also keeps "dh" (= du), "dut", "dyt"
+    and the workspaces.  Returns err_input (None without
+    ``need_err_input``)."""
+    name = "ffn_bwd"
+    ffn_act_code(act)
+    P, I, F_, E, ldx = _ffn_args(name, x, w1, w2, None)
+    dev, dt = x.device, x.dtype
+    if accumulate not in (True, "overwrite"):
+        raise ValueError("%s: accumulate must be True or \"overwrite\"" %
+                         name)
+    oshape = tuple(x.shape[:-1]) + (E,)
+    if not isinstance(err, torch.Tensor) or tuple(err.shape) != oshape or \
+            not err.is_contiguous() or err.device != dev or err.dtype != dt:
+        raise ValueError("%s: err must be a contiguous %s %s on %s" %
+                         (name, dt, oshape, dev))
+    for what, t, shape in (("dw1", dw1, (F_, I)), ("dw2", dw2, (E, F_))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or \
+                tuple(t.shape) != shape or not t.is_contiguous() or \
+                t.device != dev:
+            raise ValueError("%s: %s must be a contiguous float32 [%d][%d] "
+                             "on %s" % (name, what, shape[0], shape[1], dev))
+    if dbias is not None and (not isinstance(dbias, torch.Tensor) or
+                              dbias.dtype != torch.float32 or
+                              tuple(dbias.shape) != (F_ + E,) or
+                              not dbias.is_contiguous() or
+                              dbias.device != dev):
+        raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
+                         % (name, F_ + E, dev))
+    _rec_save_check(name, "ffn_fwd", save,
+                    (("u", (P, F_), dt), ("h", (P, F_), dt)), dev)
+    aux_act = act_code(aux_act)
+    if aux_act and aux is None:
+        raise ValueError("%s: aux_act without aux" % name)
+    if need_err_input:
+        if err_input is not None and (
+                tuple(err_input.shape) != tuple(x.shape) or
+                not err_input.is_contiguous() or err_input.device != dev or
+                err_input.dtype != dt):
+            raise ValueError("%s: err_input must be a contiguous %s %s" %
+                             (name, dt, tuple(x.shape)))
+        if aux_act and (aux.numel() != P * I or not aux.is_contiguous()):
+            raise ValueError("%s: aux must be a contiguous %s" %
+                             (name, tuple(x.shape)))
+    add = accumulate is True
+    g2 = err.view(P, E)
+    x2 = x.as_strided((P, I), (ldx, 1))
+    u, h = save["u"], save["h"]
+    db1 = None if dbias is None else dbias[:F_]
+    db2 = None if dbias is None else dbias[F_:]
+    if _ffn_wgrad_nn(g2, h):
+        gt = _rec_buf(save, "dyt", (E, P), dt, dev)
+        gws = _rec_buf(save, "dyt_ws", (P // 64 * E,), torch.float32, dev)
+        transpose_colsum(g2, out=gt, colsum=db2, accumulate=add, ws=gws)
+        gemm(gt, h, out=dw2, accumulate=accumulate)
+    else:
+        gemm(g2, h, trans_a=True, out=dw2, accumulate=accumulate,
+             bias_grad=db2)
+    dh = _rec_buf(save, "dh", (P, F_), dt, dev)
+    gemm(g2, w2, out=dh)
+    if _ffn_wgrad_nn(dh, x2):
+        dut = _rec_buf(save, "dut", (F_, P), dt, dev)
+        if _FFN_TILE:
+            ffn_act_bwd(dh, u, act, out=dh, out_t=dut, db1=db1,
+                        accumulate=accumulate, ws=save)
+        else:
+            ffn_act_bwd(dh, u, act, out=dh, ws=save)
+            tws = _rec_buf(save, "dut_ws", (P // 64 * F_,), torch.float32,
+                           dev)
+            transpose_colsum(dh, out=dut, colsum=db1, accumulate=add, ws=tws)
+        gemm(dut, x2, out=dw1, accumulate=accumulate)
+    else:
+        ffn_act_bwd(dh, u, act, out=dh, db1=db1, accumulate=accumulate,
+                    ws=save)
+        gemm(dh, x2, trans_a=True, out=dw1, accumulate=accumulate)
+    if not need_err_input:
+        return None
+    if err_input is None:
+        err_input = torch.empty(x.shape, dtype=dt, device=dev)
+    gemm(dh, w1, out=err_input.view(P, I),
+         aux=aux.reshape(P, I) if aux_act else None, aux_act=aux_act)
     return err_input

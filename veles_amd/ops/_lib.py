@@ -206,6 +206,12 @@ _OPTIONAL = {
     "hvk_ln_fwd": [P, L] * 3 + [L, I, P, P, F, P, P, P],
     "hvk_ln_bwd": [P, L] * 4 + [L, I, I, P, P, P, P, P, I, I, P, P],
     "hvk_add": [P, L] * 3 + [L, I, P],
+    # feed-forward activation passes (csrc/kernels/ffn.hip): (P, F,
+    # transposed); (u, h each with its pitch, P, F, act, s); (dh, u, du, dut
+    # each with its pitch, P, F, act, db1, accumulate, ws, s)
+    "hvk_ffn_act_partials": [L, I, I],
+    "hvk_ffn_act_fwd": [P, L] * 2 + [L, I, I, P],
+    "hvk_ffn_act_bwd": [P, L] * 4 + [L, I, I, P, I, P, P],
 }
 # functions returning a pointer / a 64-bit int (every other one returns int)
 _PTR_RET = {"hvk_stream_create"}
