@@ -36,6 +36,18 @@
 // no atomics and no workgroup waiting for another, so results repeat bit for
 // bit (docs/OPS.md "Attention").
 //
+// Dropout on P (the DROP template flag; hvk_adrop_*): P~ = P o M / (1 - p)
+// feeds the second products, the softmax statistics stay those of P.  The mask
+// is counter-based, two hashes deep: row_seed = hash32(((base_row + b) NH + h)
+// T + i, seed), M_ij = hash32(j, row_seed) >= thresh, so no index grows with
+// T^2.  fwd and dq hold the query on the lane and hash the row once per lane
+// before the sweep; dkv sweeps the queries, so the 32 row seeds of a tile go
+// to LDS at staging.  Dropped elements are selected to +0 before the bf16
+// packing; 1 / (1 - p) multiplies o and dV at the store and dP in float32
+// right after its product.  The seed is read from device memory, so a
+// captured launch carries no host value.  DROP = false is the code without
+// any of this.
+//
 // Masking: rows past T are loaded from the clamped row T-1 and masked to an
 // exact 0 in P; stores are guarded.  Every query row sees key 0 in the first
 // tile it visits, so the running maximum is finite from then on.
@@ -146,6 +158,30 @@ __device__ __forceinline__ int at_accrow(int i, int hh) {
   return (i & 3) + 8 * (i >> 2) + 4 * hh;
 }
 
+// the counter hash of elementwise.hip (dropout, stochastic pooling)
+__device__ __forceinline__ uint32_t at_hash32(uint32_t x, uint32_t seed) {
+  x ^= seed * 0x9E3779B9u;
+  x ^= x >> 16; x *= 0x7feb352du;
+  x ^= x >> 15; x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+// dropout on P: the device seed, keep iff hash >= thresh, inv = 1 / (1 - p),
+// row0 = the rank's first sample in the global minibatch (mod 2^32)
+struct AtDrop {
+  const uint32_t* seed;
+  uint32_t thresh;
+  float inv;
+  uint32_t row0;
+};
+// seed of mask row (b, h, i)
+__device__ __forceinline__ uint32_t at_rowseed(const AtDrop& dr, int b, int h,
+                                               int NH, int T, int i,
+                                               uint32_t seed) {
+  return at_hash32(((dr.row0 + (uint32_t)b) * (uint32_t)NH + (uint32_t)h) *
+                       (uint32_t)T + (uint32_t)i, seed);
+}
+
 struct AtIds {
   int tile, b, h, bh;
 };
@@ -177,14 +213,14 @@ __device__ __forceinline__ void at_store_t(uint16_t* __restrict__ dst,
 }
 
 // ---------------------------------------------------------------- forward
-template <int D, bool VEC>
+template <int D, bool VEC, bool DROP>
 __global__ void __launch_bounds__(AT_THREADS)
 attn_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
                 const uint16_t* __restrict__ k, long long ldk,
                 const uint16_t* __restrict__ v, long long ldv,
                 uint16_t* __restrict__ o, long long ldo,
                 float* __restrict__ lse, int T, int NH, int ntiles, int causal,
-                float c2) {
+                float c2, AtDrop dr) {
   __shared__ __attribute__((aligned(16))) uint16_t kimg[32 * D];
   __shared__ __attribute__((aligned(16))) uint16_t vtimg[D * AT_TRP];
   const AtIds id = at_ids(ntiles, NH, true);
@@ -207,6 +243,10 @@ attn_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
 #pragma unroll
   for (int db = 0; db < D / 32; ++db) oacc[db] = at_zero();
   float m = -INFINITY, l = 0.f;
+  uint32_t rseed = 0;
+  if constexpr (DROP)
+    rseed = at_rowseed(dr, id.b, id.h, NH, T, qi,
+                       __builtin_amdgcn_readfirstlane(dr.seed[0]));
   const int klast = causal ? min(T - 1, q0 + AT_OWN - 1) : T - 1;
   const int nkt = klast / AT_SWEEP + 1;
   for (int kt = 0; kt < nkt; ++kt) {
@@ -249,6 +289,12 @@ attn_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
     for (int db = 0; db < D / 32; ++db)
 #pragma unroll
       for (int i = 0; i < 16; ++i) oacc[db][i] *= alpha;
+    if constexpr (DROP) {   // l took the undropped exponentials
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (at_hash32((uint32_t)(k0 + at_accrow(i, hh)), rseed) < dr.thresh)
+          p[i] = 0.f;
+    }
     const bf16x8 pb[2] = {at_pack8(p), at_pack8(p + 8)};
 #pragma unroll
     for (int db = 0; db < D / 32; ++db)
@@ -258,7 +304,7 @@ attn_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
                            oacc[db]);
   }
   if (wave_on && qi < T) {
-    at_store_t<D, VEC>(o, ldo, qi, hh, oacc, 1.f / l);
+    at_store_t<D, VEC>(o, ldo, qi, hh, oacc, DROP ? dr.inv / l : 1.f / l);
     if (hh == 0) lse[(long long)id.bh * T + qi] = m * AT_LN2 + logf(l);
   }
 }
@@ -298,7 +344,7 @@ attn_delta_kernel(const uint16_t* __restrict__ dout, long long lddo,
 }
 
 // --------------------------------------------------------------------- dq
-template <int D, bool VEC>
+template <int D, bool VEC, bool DROP>
 __global__ void __launch_bounds__(AT_THREADS)
 attn_dq_kernel(const uint16_t* __restrict__ q, long long ldq,
                const uint16_t* __restrict__ k, long long ldk,
@@ -306,7 +352,7 @@ attn_dq_kernel(const uint16_t* __restrict__ q, long long ldq,
                const uint16_t* __restrict__ dout, long long lddo,
                const float* __restrict__ lse, const float* __restrict__ delta,
                uint16_t* __restrict__ dq, long long lddq, int T, int NH,
-               int ntiles, int causal, float c2, float scale) {
+               int ntiles, int causal, float c2, float scale, AtDrop dr) {
   __shared__ __attribute__((aligned(16))) uint16_t kimg[32 * D];
   __shared__ __attribute__((aligned(16))) uint16_t vimg[32 * D];
   __shared__ __attribute__((aligned(16))) uint16_t ktimg[D * AT_TRP];
@@ -332,6 +378,10 @@ attn_dq_kernel(const uint16_t* __restrict__ q, long long ldq,
   }
   const float lse2 = lse[(long long)id.bh * T + qc] * AT_LOG2E;
   const float dl = delta[(long long)id.bh * T + qc];
+  uint32_t rseed = 0;
+  if constexpr (DROP)
+    rseed = at_rowseed(dr, id.b, id.h, NH, T, qi,
+                       __builtin_amdgcn_readfirstlane(dr.seed[0]));
   f32x16 acc[D / 32];
 #pragma unroll
   for (int db = 0; db < D / 32; ++db) acc[db] = at_zero();
@@ -359,7 +409,11 @@ attn_dq_kernel(const uint16_t* __restrict__ q, long long ldq,
         const int key = k0 + at_accrow(i, hh);
         if (key >= T || (causal && key > qi)) pv = 0.f;
       }
-      ds[i] = pv * (pacc[i] - dl) * scale;
+      float dp = pacc[i];
+      if constexpr (DROP)
+        dp = at_hash32((uint32_t)(k0 + at_accrow(i, hh)), rseed) >= dr.thresh
+                 ? dp * dr.inv : 0.f;
+      ds[i] = pv * (dp - dl) * scale;
     }
     const bf16x8 dsb[2] = {at_pack8(ds), at_pack8(ds + 8)};
 #pragma unroll
@@ -373,7 +427,7 @@ attn_dq_kernel(const uint16_t* __restrict__ q, long long ldq,
 }
 
 // -------------------------------------------------------------------- dkv
-template <int D, bool VEC>
+template <int D, bool VEC, bool DROP>
 __global__ void __launch_bounds__(AT_THREADS)
 attn_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
                 const uint16_t* __restrict__ k, long long ldk,
@@ -382,12 +436,13 @@ attn_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
                 const float* __restrict__ lse, const float* __restrict__ delta,
                 uint16_t* __restrict__ dk, long long lddk,
                 uint16_t* __restrict__ dv, long long lddv, int T, int NH,
-                int ntiles, int causal, float c2, float scale) {
+                int ntiles, int causal, float c2, float scale, AtDrop dr) {
   __shared__ __attribute__((aligned(16))) uint16_t qimg[32 * D];
   __shared__ __attribute__((aligned(16))) uint16_t doimg[32 * D];
   __shared__ __attribute__((aligned(16))) uint16_t qtimg[D * AT_TRP];
   __shared__ __attribute__((aligned(16))) uint16_t dotimg[D * AT_TRP];
   __shared__ float rowc[2][AT_SWEEP];   // lse * log2(e), delta of the tile
+  __shared__ uint32_t rowsd[DROP ? AT_SWEEP : 1];   // mask row seeds of it
   const AtIds id = at_ids(ntiles, NH, false);
   const long long row0 = (long long)id.b * T;
   q += row0 * ldq + id.h * D;
@@ -411,6 +466,8 @@ attn_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
     vf[s] = __builtin_bit_cast(
         bf16x8, at_ld8<VEC>(v + (long long)kc * ldv + 16 * s + 8 * hh));
   }
+  uint32_t seed = 0;
+  if constexpr (DROP) seed = __builtin_amdgcn_readfirstlane(dr.seed[0]);
   f32x16 dkacc[D / 32], dvacc[D / 32];
 #pragma unroll
   for (int db = 0; db < D / 32; ++db) dkacc[db] = dvacc[db] = at_zero();
@@ -425,6 +482,11 @@ attn_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
       const int t = min(qt0 + (int)(threadIdx.x & 31), T - 1);
       rowc[threadIdx.x >> 5][threadIdx.x & 31] =
           threadIdx.x < AT_SWEEP ? lse[t] * AT_LOG2E : delta[t];
+    }
+    if constexpr (DROP) {   // in wave 1: wave 0 loads rowc
+      if (threadIdx.x >= 3 * AT_SWEEP && threadIdx.x < 4 * AT_SWEEP)
+        rowsd[threadIdx.x & 31] = at_rowseed(
+            dr, id.b, id.h, NH, T, qt0 + (int)(threadIdx.x & 31), seed);
     }
     __syncthreads();
     if (!wave_on || (causal && qt0 < wk0)) continue;   // wave-uniform
@@ -445,8 +507,15 @@ attn_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
         const int qrow = qt0 + qr;
         if (qrow >= T || kj >= T || (causal && kj > qrow)) pv = 0.f;
       }
-      p[i] = pv;
-      ds[i] = pv * (pacc[i] - rowc[1][qr]) * scale;
+      float dp = pacc[i];
+      if constexpr (DROP) {
+        const bool keep = at_hash32((uint32_t)kj, rowsd[qr]) >= dr.thresh;
+        p[i] = keep ? pv : 0.f;
+        dp = keep ? dp * dr.inv : 0.f;
+      } else {
+        p[i] = pv;
+      }
+      ds[i] = pv * (dp - rowc[1][qr]) * scale;
     }
     const bf16x8 pb[2] = {at_pack8(p), at_pack8(p + 8)};
     const bf16x8 dsb[2] = {at_pack8(ds), at_pack8(ds + 8)};
@@ -462,7 +531,7 @@ attn_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
   }
   if (wave_on && kj < T) {
     at_store_t<D, VEC>(dk, lddk, kj, hh, dkacc, 1.f);
-    at_store_t<D, VEC>(dv, lddv, kj, hh, dvacc, 1.f);
+    at_store_t<D, VEC>(dv, lddv, kj, hh, dvacc, DROP ? dr.inv : 1.f);
   }
 }
 
@@ -484,30 +553,113 @@ inline bool at_shape_ok(int B, int T, int NH, int D) {
 }
 inline float at_scale(int D) { return 1.f / sqrtf((float)D); }
 
-#define HVK_AT_DISPATCH(KERNEL, grid, ...)                                   \
-  do {                                                                       \
-    if (vec) {                                                               \
-      if (D == 32)                                                           \
-        hipLaunchKernelGGL((KERNEL<32, true>), grid, dim3(AT_THREADS), 0, s, \
-                           __VA_ARGS__);                                     \
-      else if (D == 64)                                                      \
-        hipLaunchKernelGGL((KERNEL<64, true>), grid, dim3(AT_THREADS), 0, s, \
-                           __VA_ARGS__);                                     \
-      else                                                                   \
-        hipLaunchKernelGGL((KERNEL<128, true>), grid, dim3(AT_THREADS), 0,   \
-                           s, __VA_ARGS__);                                  \
-    } else {                                                                 \
-      if (D == 32)                                                           \
-        hipLaunchKernelGGL((KERNEL<32, false>), grid, dim3(AT_THREADS), 0,   \
-                           s, __VA_ARGS__);                                  \
-      else if (D == 64)                                                      \
-        hipLaunchKernelGGL((KERNEL<64, false>), grid, dim3(AT_THREADS), 0,   \
-                           s, __VA_ARGS__);                                  \
-      else                                                                   \
-        hipLaunchKernelGGL((KERNEL<128, false>), grid, dim3(AT_THREADS), 0,  \
-                           s, __VA_ARGS__);                                  \
-    }                                                                        \
+// KERNEL<D, VEC TAIL> by the runtime D and vec; TAIL is empty or HVK_AT_DROP
+#define HVK_AT_DROP , DROP
+#define HVK_AT_LAUNCH(K, grid, ...) \
+  hipLaunchKernelGGL(K, grid, dim3(AT_THREADS), 0, s, __VA_ARGS__)
+#define HVK_AT_DISPATCH(KERNEL, TAIL, grid, ...)                       \
+  do {                                                                 \
+    if (vec) {                                                         \
+      if (D == 32)                                                     \
+        HVK_AT_LAUNCH((KERNEL<32, true TAIL>), grid, __VA_ARGS__);       \
+      else if (D == 64)                                                \
+        HVK_AT_LAUNCH((KERNEL<64, true TAIL>), grid, __VA_ARGS__);       \
+      else                                                             \
+        HVK_AT_LAUNCH((KERNEL<128, true TAIL>), grid, __VA_ARGS__);      \
+    } else {                                                           \
+      if (D == 32)                                                     \
+        HVK_AT_LAUNCH((KERNEL<32, false TAIL>), grid, __VA_ARGS__);      \
+      else if (D == 64)                                                \
+        HVK_AT_LAUNCH((KERNEL<64, false TAIL>), grid, __VA_ARGS__);      \
+      else                                                             \
+        HVK_AT_LAUNCH((KERNEL<128, false TAIL>), grid, __VA_ARGS__);     \
+    }                                                                  \
   } while (0)
+
+// keep iff hash >= floor(p 2^32) from the float32 p (the rule of
+// hvk_dropout*); false for p outside [0, 1) or a null seed
+inline bool at_drop_ok(const uint32_t* seed_dev, float p, long long base_row,
+                       AtDrop* dr) {
+  if (!seed_dev || !(p >= 0.f) || !(p < 1.f)) return false;
+  dr->seed = seed_dev;
+  dr->thresh = (uint32_t)((double)p * 4294967296.0);
+  dr->inv = 1.f / (1.f - p);
+  dr->row0 = (uint32_t)(unsigned long long)base_row;
+  return true;
+}
+
+template <bool DROP>
+int at_fwd(const void* q, long long ldq, const void* k, long long ldk,
+           const void* v, long long ldv, void* o, long long ldo, float* lse,
+           int B, int T, int NH, int D, int causal, AtDrop dr,
+           hipStream_t s) {
+  if (!at_shape_ok(B, T, NH, D) || !lse) return -1;
+  const long long rows = (long long)B * T;
+  const int E = NH * D;
+  if (!at_view_ok(q, ldq, rows, E) || !at_view_ok(k, ldk, rows, E) ||
+      !at_view_ok(v, ldv, rows, E) || !at_view_ok(o, ldo, rows, E))
+    return -1;
+  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
+                   at_on16(o, ldo);
+  const int ntiles = (T + AT_OWN - 1) / AT_OWN;
+  const dim3 grid((unsigned)((long long)ntiles * B * NH));
+  HVK_AT_DISPATCH(attn_fwd_kernel, HVK_AT_DROP, grid, (const uint16_t*)q, ldq,
+                  (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
+                  (uint16_t*)o, ldo, lse, T, NH, ntiles, causal != 0,
+                  at_scale(D) * AT_LOG2E, dr);
+  return (int)launch_status(s);
+}
+
+template <bool DROP>
+int at_bwd_dkv(const void* q, long long ldq, const void* k, long long ldk,
+               const void* v, long long ldv, const void* dout, long long lddo,
+               const float* lse, const float* delta, void* dk, long long lddk,
+               void* dv, long long lddv, int B, int T, int NH, int D,
+               int causal, AtDrop dr, hipStream_t s) {
+  if (!at_shape_ok(B, T, NH, D) || !lse || !delta) return -1;
+  const long long rows = (long long)B * T;
+  const int E = NH * D;
+  if (!at_view_ok(q, ldq, rows, E) || !at_view_ok(k, ldk, rows, E) ||
+      !at_view_ok(v, ldv, rows, E) || !at_view_ok(dout, lddo, rows, E) ||
+      !at_view_ok(dk, lddk, rows, E) || !at_view_ok(dv, lddv, rows, E))
+    return -1;
+  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
+                   at_on16(dout, lddo) && at_on16(dk, lddk) &&
+                   at_on16(dv, lddv);
+  const int ntiles = (T + AT_OWN - 1) / AT_OWN;
+  const dim3 grid((unsigned)((long long)ntiles * B * NH));
+  HVK_AT_DISPATCH(attn_dkv_kernel, HVK_AT_DROP, grid, (const uint16_t*)q, ldq,
+                  (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
+                  (const uint16_t*)dout, lddo, lse, delta, (uint16_t*)dk, lddk,
+                  (uint16_t*)dv, lddv, T, NH, ntiles, causal != 0,
+                  at_scale(D) * AT_LOG2E, at_scale(D), dr);
+  return (int)launch_status(s);
+}
+
+template <bool DROP>
+int at_bwd_dq(const void* q, long long ldq, const void* k, long long ldk,
+              const void* v, long long ldv, const void* dout, long long lddo,
+              const float* lse, const float* delta, void* dq, long long lddq,
+              int B, int T, int NH, int D, int causal, AtDrop dr,
+              hipStream_t s) {
+  if (!at_shape_ok(B, T, NH, D) || !lse || !delta) return -1;
+  const long long rows = (long long)B * T;
+  const int E = NH * D;
+  if (!at_view_ok(q, ldq, rows, E) || !at_view_ok(k, ldk, rows, E) ||
+      !at_view_ok(v, ldv, rows, E) || !at_view_ok(dout, lddo, rows, E) ||
+      !at_view_ok(dq, lddq, rows, E))
+    return -1;
+  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
+                   at_on16(dout, lddo) && at_on16(dq, lddq);
+  const int ntiles = (T + AT_OWN - 1) / AT_OWN;
+  const dim3 grid((unsigned)((long long)ntiles * B * NH));
+  HVK_AT_DISPATCH(attn_dq_kernel, HVK_AT_DROP, grid, (const uint16_t*)q, ldq,
+                  (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
+                  (const uint16_t*)dout, lddo, lse, delta, (uint16_t*)dq, lddq,
+                  T, NH, ntiles, causal != 0, at_scale(D) * AT_LOG2E,
+                  at_scale(D), dr);
+  return (int)launch_status(s);
+}
 
 }  // namespace
 
@@ -522,21 +674,8 @@ HVK_API int hvk_attn_fwd(const void* q, long long ldq, const void* k,
                          long long ldk, const void* v, long long ldv, void* o,
                          long long ldo, float* lse, int B, int T, int NH,
                          int D, int causal, hipStream_t s) {
-  if (!at_shape_ok(B, T, NH, D) || !lse) return -1;
-  const long long rows = (long long)B * T;
-  const int E = NH * D;
-  if (!at_view_ok(q, ldq, rows, E) || !at_view_ok(k, ldk, rows, E) ||
-      !at_view_ok(v, ldv, rows, E) || !at_view_ok(o, ldo, rows, E))
-    return -1;
-  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
-                   at_on16(o, ldo);
-  const int ntiles = (T + AT_OWN - 1) / AT_OWN;
-  const dim3 grid((unsigned)((long long)ntiles * B * NH));
-  HVK_AT_DISPATCH(attn_fwd_kernel, grid, (const uint16_t*)q, ldq,
-                  (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
-                  (uint16_t*)o, ldo, lse, T, NH, ntiles, causal != 0,
-                  at_scale(D) * AT_LOG2E);
-  return (int)launch_status(s);
+  return at_fwd<false>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, T, NH, D,
+                       causal, AtDrop{}, s);
 }
 
 // delta [B][NH][T] = rowsum over a head's columns of do * o
@@ -552,7 +691,7 @@ HVK_API int hvk_attn_bwd_delta(const void* dout, long long lddo,
   const long long nrows = rows * NH;
   const long long threads = nrows * (D / 8);
   const dim3 grid((unsigned)((threads + AT_THREADS - 1) / AT_THREADS));
-  HVK_AT_DISPATCH(attn_delta_kernel, grid, (const uint16_t*)dout, lddo,
+  HVK_AT_DISPATCH(attn_delta_kernel, , grid, (const uint16_t*)dout, lddo,
                   (const uint16_t*)o, ldo, delta, T, NH, nrows);
   return (int)launch_status(s);
 }
@@ -565,24 +704,8 @@ HVK_API int hvk_attn_bwd_dkv(const void* q, long long ldq, const void* k,
                              const float* lse, const float* delta, void* dk,
                              long long lddk, void* dv, long long lddv, int B,
                              int T, int NH, int D, int causal, hipStream_t s) {
-  if (!at_shape_ok(B, T, NH, D) || !lse || !delta) return -1;
-  const long long rows = (long long)B * T;
-  const int E = NH * D;
-  if (!at_view_ok(q, ldq, rows, E) || !at_view_ok(k, ldk, rows, E) ||
-      !at_view_ok(v, ldv, rows, E) || !at_view_ok(dout, lddo, rows, E) ||
-      !at_view_ok(dk, lddk, rows, E) || !at_view_ok(dv, lddv, rows, E))
-    return -1;
-  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
-                   at_on16(dout, lddo) && at_on16(dk, lddk) &&
-                   at_on16(dv, lddv);
-  const int ntiles = (T + AT_OWN - 1) / AT_OWN;
-  const dim3 grid((unsigned)((long long)ntiles * B * NH));
-  HVK_AT_DISPATCH(attn_dkv_kernel, grid, (const uint16_t*)q, ldq,
-                  (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
-                  (const uint16_t*)dout, lddo, lse, delta, (uint16_t*)dk, lddk,
-                  (uint16_t*)dv, lddv, T, NH, ntiles, causal != 0,
-                  at_scale(D) * AT_LOG2E, at_scale(D));
-  return (int)launch_status(s);
+  return at_bwd_dkv<false>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk,
+                           lddk, dv, lddv, B, T, NH, D, causal, AtDrop{}, s);
 }
 
 // dq from the same operands
@@ -592,21 +715,50 @@ HVK_API int hvk_attn_bwd_dq(const void* q, long long ldq, const void* k,
                             const float* delta, void* dq, long long lddq,
                             int B, int T, int NH, int D, int causal,
                             hipStream_t s) {
-  if (!at_shape_ok(B, T, NH, D) || !lse || !delta) return -1;
-  const long long rows = (long long)B * T;
-  const int E = NH * D;
-  if (!at_view_ok(q, ldq, rows, E) || !at_view_ok(k, ldk, rows, E) ||
-      !at_view_ok(v, ldv, rows, E) || !at_view_ok(dout, lddo, rows, E) ||
-      !at_view_ok(dq, lddq, rows, E))
-    return -1;
-  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
-                   at_on16(dout, lddo) && at_on16(dq, lddq);
-  const int ntiles = (T + AT_OWN - 1) / AT_OWN;
-  const dim3 grid((unsigned)((long long)ntiles * B * NH));
-  HVK_AT_DISPATCH(attn_dq_kernel, grid, (const uint16_t*)q, ldq,
-                  (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
-                  (const uint16_t*)dout, lddo, lse, delta, (uint16_t*)dq, lddq,
-                  T, NH, ntiles, causal != 0, at_scale(D) * AT_LOG2E,
-                  at_scale(D));
-  return (int)launch_status(s);
+  return at_bwd_dq<false>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq,
+                          lddq, B, T, NH, D, causal, AtDrop{}, s);
+}
+
+// The three kernels with dropout on P at probability p in [0, 1): the mask of
+// (b, h, i, j) is hash32(j, hash32(((base_row + b) NH + h) T + i, seed)) >=
+// floor(p 2^32) with the seed read from seed_dev[0] on the device.  o and lse
+// of hvk_adrop_fwd (lse is that of the undropped scores) and
+// hvk_attn_bwd_delta's delta feed the two backward entries, which must see
+// the seed value the forward saw.  -1 on p outside [0, 1) or a null seed.
+HVK_API int hvk_adrop_fwd(const void* q, long long ldq, const void* k,
+                          long long ldk, const void* v, long long ldv, void* o,
+                          long long ldo, float* lse, int B, int T, int NH,
+                          int D, int causal, const uint32_t* seed_dev, float p,
+                          long long base_row, hipStream_t s) {
+  AtDrop dr;
+  if (!at_drop_ok(seed_dev, p, base_row, &dr)) return -1;
+  return at_fwd<true>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, T, NH, D,
+                      causal, dr, s);
+}
+
+HVK_API int hvk_adrop_bwd_dkv(const void* q, long long ldq, const void* k,
+                              long long ldk, const void* v, long long ldv,
+                              const void* dout, long long lddo,
+                              const float* lse, const float* delta, void* dk,
+                              long long lddk, void* dv, long long lddv, int B,
+                              int T, int NH, int D, int causal,
+                              const uint32_t* seed_dev, float p,
+                              long long base_row, hipStream_t s) {
+  AtDrop dr;
+  if (!at_drop_ok(seed_dev, p, base_row, &dr)) return -1;
+  return at_bwd_dkv<true>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk,
+                          lddk, dv, lddv, B, T, NH, D, causal, dr, s);
+}
+
+HVK_API int hvk_adrop_bwd_dq(const void* q, long long ldq, const void* k,
+                             long long ldk, const void* v, long long ldv,
+                             const void* dout, long long lddo,
+                             const float* lse, const float* delta, void* dq,
+                             long long lddq, int B, int T, int NH, int D,
+                             int causal, const uint32_t* seed_dev, float p,
+                             long long base_row, hipStream_t s) {
+  AtDrop dr;
+  if (!at_drop_ok(seed_dev, p, base_row, &dr)) return -1;
+  return at_bwd_dq<true>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq,
+                         lddq, B, T, NH, D, causal, dr, s);
 }

@@ -94,6 +94,28 @@ int hvk_attn_bwd_dq(const void* q, long long ldq, const void* k,
                     const void* dout, long long lddo, const float* lse,
                     const float* delta, void* dq, long long lddq, int B, int T,
                     int NH, int D, int causal, hipStream_t s);
+// the same three kernels with dropout on P: mask (b, h, i, j) = hash32(j,
+// hash32(((base_row + b) NH + h) T + i, seed_dev[0])) >= floor(p 2^32),
+// p in [0, 1)
+int hvk_adrop_fwd(const void* q, long long ldq, const void* k, long long ldk,
+                  const void* v, long long ldv, void* o, long long ldo,
+                  float* lse, int B, int T, int NH, int D, int causal,
+                  const uint32_t* seed_dev, float p, long long base_row,
+                  hipStream_t s);
+int hvk_adrop_bwd_dkv(const void* q, long long ldq, const void* k,
+                      long long ldk, const void* v, long long ldv,
+                      const void* dout, long long lddo, const float* lse,
+                      const float* delta, void* dk, long long lddk, void* dv,
+                      long long lddv, int B, int T, int NH, int D, int causal,
+                      const uint32_t* seed_dev, float p, long long base_row,
+                      hipStream_t s);
+int hvk_adrop_bwd_dq(const void* q, long long ldq, const void* k,
+                     long long ldk, const void* v, long long ldv,
+                     const void* dout, long long lddo, const float* lse,
+                     const float* delta, void* dq, long long lddq, int B,
+                     int T, int NH, int D, int causal,
+                     const uint32_t* seed_dev, float p, long long base_row,
+                     hipStream_t s);
 int hvk_act_fwd(const void* x, int xdt, void* y, int ydt, long long n, int act,
                 hipStream_t s);
 int hvk_softmax_ce(const void* logits, int in_dt, int B, int C,

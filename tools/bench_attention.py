@@ -20,7 +20,13 @@ Acceptance (docs/OPS.md "Attention"): at every shape the forward + backward
 median of (a) is below (b)'s by more than the two round-to-round spreads
 (max - min) added together.
 
-    python tools/bench_attention.py [--rounds 7] [--out FILE]
+With ``--dropout P`` the variants are instead (a) at p = 0, (d) the fused
+kernels with dropout P on the attention weights (``hvk_adrop_*``; the device
+seed is advanced in every call, as the layer does) and (c) SDPA with
+``dropout_p=P``; the summary is (d) - (a) against the two spreads, and
+(c) / (d).
+
+    python tools/bench_attention.py [--rounds 7] [--dropout P] [--out FILE]
 """
 import argparse
 import json
@@ -85,7 +91,7 @@ def graphed(fn):
         return None
 
 
-def variants(B, T, NH, D, causal, dev):
+def variants(B, T, NH, D, causal, dev, drop=0.0):
     E = NH * D
     gen = torch.Generator(device=dev).manual_seed(1)
     qkv = torch.randn(B, T, 3 * E, device=dev, generator=gen).bfloat16()
@@ -118,7 +124,21 @@ def variants(B, T, NH, D, causal, dev):
         return torch.softmax(s, 3) @ th[2]
 
     def sdpa():
-        return F.scaled_dot_product_attention(*th, is_causal=causal)
+        return F.scaled_dot_product_attention(*th, is_causal=causal,
+                                              dropout_p=drop)
+
+    sd = torch.tensor([12345], dtype=torch.int32, device=dev)
+    dsave, dws = {}, {}
+    dkw = dict(causal=causal, dropout=drop, seed_dev=sd)
+
+    def d_fwd():
+        ops.seed_advance(sd)
+        ops.attention_fwd(q, k, v, NH, out=o, save=dsave, **dkw)
+
+    def d_both():
+        d_fwd()
+        ops.attention_bwd(do, q, k, v, o, dsave, NH, dq=dq, dk=dk, dv=dv,
+                          ws=dws, **dkw)
 
     def fwd_of(f):
         def run():
@@ -132,9 +152,12 @@ def variants(B, T, NH, D, causal, dev):
         return run
 
     out = []
-    for name, f, b in (("a fused", a_fwd, a_both),
-                       ("b unfused torch", fwd_of(unfused), both_of(unfused)),
-                       ("c torch sdpa", fwd_of(sdpa), both_of(sdpa))):
+    rows = [("a fused", a_fwd, a_both),
+            ("b unfused torch", fwd_of(unfused), both_of(unfused)),
+            ("c torch sdpa", fwd_of(sdpa), both_of(sdpa))]
+    if drop:
+        rows[1] = ("d fused dropout", d_fwd, d_both)
+    for name, f, b in rows:
         for what, fn in (("fwd", f), ("fwd+bwd", b)):
             out.append(("%s %s eager" % (name, what), what, fn))
             g = graphed(fn)
@@ -147,6 +170,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="compare the fused kernels at this drop "
+                    "probability with p = 0 and with SDPA's dropout_p")
     ap.add_argument("--shapes", default=None,
                     help="indices into SHAPES, e.g. 0,1")
     a = ap.parse_args(argv)
@@ -161,11 +187,14 @@ def main(argv=None):
         lines.append(s)
     say("%d rounds per variant, first round untimed; SDPA backends that run "
         "here: %s" % (a.rounds, ", ".join(sdpa_backends(dev)) or "none"))
+    if a.dropout:
+        say("dropout %g: (d) fused with dropout, (c) SDPA with dropout_p" %
+            a.dropout)
     shapes = SHAPES if a.shapes is None else \
         [SHAPES[int(i)] for i in a.shapes.split(",")]
     for B, T, NH, D in shapes:
         for causal in (False, True):
-            vs = variants(B, T, NH, D, causal, dev)
+            vs = variants(B, T, NH, D, causal, dev, a.dropout)
             flop = 4.0 * B * NH * T * T * D * (0.5 if causal else 1.0)
             calls = max(2, min(50, int(2e10 / flop)))
             times = {name: [] for name, _, _ in vs}
@@ -198,7 +227,20 @@ def main(argv=None):
                 say("  %-34s %10.1f %10.1f %10.1f %8.1f" % (
                     name, row["median_us"], row["min_us"], row["max_us"],
                     row["tf_per_s"]))
-            for mode in ("eager", "graph"):
+            for mode in ("eager", "graph") if a.dropout else ():
+                ra = med.get("a fused fwd+bwd " + mode)
+                rd = med.get("d fused dropout fwd+bwd " + mode)
+                rc = med.get("c torch sdpa fwd+bwd " + mode)
+                if ra and rd:
+                    spread = (ra["max_us"] - ra["min_us"]) + \
+                        (rd["max_us"] - rd["min_us"])
+                    say("  fwd+bwd %s: (d) - (a) = %.1f us, spreads added "
+                        "%.1f us; (d) / (a) = %.3f%s" % (
+                            mode, rd["median_us"] - ra["median_us"], spread,
+                            rd["median_us"] / ra["median_us"],
+                            "" if not rc else ", (c) / (d) = %.2f" % (
+                                rc["median_us"] / rd["median_us"])))
+            for mode in () if a.dropout else ("eager", "graph"):
                 ra = med.get("a fused fwd+bwd " + mode)
                 rb = med.get("b unfused torch fwd+bwd " + mode)
                 rc = med.get("c torch sdpa fwd+bwd " + mode)

@@ -1,8 +1,10 @@
 """Multi-head scaled dot-product self-attention (``attention`` layer type;
 docs/OPS.md "Attention").  Znicz has no such layer, so the semantics are this
 project's own, pinned to ``torch.nn.MultiheadAttention(E, NH, bias=True,
-dropout=0, batch_first=True)`` applied to (x, x, x), with a causal
-``attn_mask`` when ``causal`` is set (parity unpinned).
+dropout=p, batch_first=True)`` applied to (x, x, x), with a causal
+``attn_mask`` when ``causal`` is set (parity unpinned); p = ``dropout``
+(default 0) drops attention weights on TRAIN minibatches with this project's
+counter-based mask, not torch's generator.
 
 Input samples are (T, I), batch-major [B][T][I] as for the recurrent layers;
 the output is (T, E) with E = ``output_sample_shape``, NH = ``heads`` and
@@ -19,6 +21,14 @@ one ``bias`` is [4E] = (b_q, b_k, b_v, b_o): with I = E they are torch's
 with fan-in E; the biases start at 0.  The forward is two GEMMs around the
 fused attention kernel (``ops.mha_fwd``), the backward five GEMMs around the
 three backward kernels (``ops.mha_bwd``).
+
+Dropout: o = (P o M / (1 - p)) v inside the fused kernels (P never exists in
+memory, so no ``dropout`` layer can reach it).  As for ``DropoutForward`` the
+seed lives on the device and is advanced once per forward (a captured step
+draws a fresh mask every replay), a snapshot resumes the mask stream exactly,
+and rank r of a data-parallel run draws the rows of samples r B .. r B + B - 1
+of the global minibatch.  Identity when the workflow is testing and on
+non-TRAIN minibatches.
 """
 from __future__ import annotations
 
@@ -26,6 +36,7 @@ import numpy
 
 from veles_amd.models.nn_units import (
     Forward, GradientDescentBase, fill_weights)
+from veles_amd.prng import device_seed
 from veles_amd import ops
 
 __all__ = ["Attention", "GDAttention"]
@@ -47,6 +58,12 @@ class Attention(Forward):
         self.width = int(oss)
         self.heads = int(kwargs.get("heads", 1))
         self.causal = bool(kwargs.get("causal", False))
+        self.dropout = float(kwargs.get("dropout", 0.0))
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError("%s: dropout must be in [0, 1), got %s" %
+                             (self.name, self.dropout))
+        self.seed = 0
+        self.seed_dev_saved = None
         if self.weights_transposed:
             raise ValueError("%s: weights_transposed is not supported" %
                              self.name)
@@ -54,6 +71,34 @@ class Attention(Forward):
     def init_unpickled(self):
         super().init_unpickled()
         self.save_ = {}
+        self.seed_dev_ = None
+        self.drop_ = {}
+
+    def __getstate__(self):
+        device_seed.save(self)   # exact resume of the device mask stream
+        return super().__getstate__()
+
+    def _draw_seed(self):
+        self.seed = int(self.rand.randint(0, 2 ** 31 - 1))
+        return self.seed
+
+    def drop_args(self, x, testing):
+        """The dropout arguments of this minibatch's ``ops.mha_fwd`` and
+        ``ops.mha_bwd``: none unless training on a TRAIN minibatch (the rule
+        of ``DropoutForward.run``).  Draws or advances the seed."""
+        mc = getattr(self, "minibatch_class", None)
+        if testing or self.dropout <= 0 or (mc is not None and mc != 2):
+            return {}
+        ld = getattr(self.workflow, "loader", None)
+        rank = int(getattr(ld, "rank", 0) or 0) if ld is not None else 0
+        kw = {"dropout": self.dropout, "base_row": rank * x.shape[0]}
+        if x.is_cuda:
+            sd = device_seed.get(self, x.device, self._draw_seed)
+            ops.seed_advance(sd)
+            kw["seed_dev"] = sd
+        else:
+            kw["seed"] = self._draw_seed()
+        return kw
 
     @property
     def neurons_number(self):
@@ -107,9 +152,10 @@ class Attention(Forward):
         testing = bool(getattr(self.workflow, "testing", False))
         y = self.alloc_output((x.shape[0],) + self.output_sample_shape,
                               w.dtype)
+        self.drop_ = self.drop_args(x, testing)
         ops.mha_fwd(x, w_in, w_out, self.bias_master, self.heads,
                     causal=self.causal, save=None if testing else self.save_,
-                    ws=self.save_, out=y)
+                    ws=self.save_, out=y, **self.drop_)
 
 
 class GDAttention(GradientDescentBase):
@@ -149,5 +195,5 @@ class GDAttention(GradientDescentBase):
                     None if pb is None else pb.grad, fwd.heads,
                     causal=fwd.causal, accumulate=mode,
                     need_err_input=self.need_err_input, err_input=ei,
-                    aux=aux, aux_act=aux_act)
+                    aux=aux, aux_act=aux_act, **fwd.drop_)
         self.report_gradients()

@@ -307,7 +307,8 @@ class StandardWorkflow(LinkBuilders, AcceleratedWorkflow):
             else:
                 unit.link_from(prev)
                 unit.link_attrs(prev, ("input", "output"))
-            if isinstance(unit, (DropoutForward, bn_units.BatchNorm)):
+            if isinstance(unit, (DropoutForward, bn_units.BatchNorm,
+                                 Attention)):
                 unit.link_attrs(self.loader, "minibatch_class")
             # encoder/decoder pairing (auto-encoders): depooling inverts the
             # latest pooling, deconv the latest conv (LIFO)

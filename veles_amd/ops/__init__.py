@@ -35,6 +35,7 @@ __all__ = ["ACT", "gemm", "linear_fwd", "conv_out_size", "conv_fwd",
            "rbm_layout", "rbm_uniforms", "rbm_sample", "rbm_grad",
            "bn_partials", "batchnorm_fwd", "batchnorm_bwd", "attention_fwd",
            "attention_bwd", "mha_fwd", "mha_bwd", "attn_head_dim",
+           "attention_dropout_mask_ref",
            "ln_partials", "layernorm_fwd", "layernorm_bwd", "add",
            "FFN_ACT", "ffn_partials", "ffn_act_fwd", "ffn_act_bwd",
            "ffn_fwd", "ffn_bwd", "set_ffn_tile"]
@@ -4142,7 +4143,62 @@ def _attn_mask(T, dev):
     return i.view(1, T) > i.view(T, 1)
 
 
-def attention_fwd(q, k, v, heads, causal=False, out=None, save=None):
+def attention_dropout_mask_ref(B, NH, T, seed, p, base_row=0):
+    """The keep mask of dropout on the attention weights, bool
+    [B][NH][T][T] (host): ``M_ij = hash32(j, row_seed) >= dropout_thresh(p)``
+    with ``row_seed = hash32(((base_row + b) NH + h) T + i, seed)``, the row
+    index truncated to 32 bits.  ``base_row``: the rank's first sample in the
+    global minibatch."""
+    M = 0xFFFFFFFF
+    ar = lambda n: torch.arange(n, dtype=torch.int64)   # noqa: E731
+    b = (ar(B) + (int(base_row) & M)) & M
+    r = ((b.view(B, 1, 1) * int(NH) + ar(NH).view(1, NH, 1)) & M) * int(T)
+    rs = _hash32((r + ar(T).view(1, 1, T)) & M, int(seed) & M)
+    # row_seed * 0x9E3779B9 mod 2^32 in halves: the product leaves int64
+    c = 0x9E3779B9
+    mul = ((rs & 0xFFFF) * c + ((((rs >> 16) * c) & 0xFFFF) << 16)) & M
+    h = _hash32(ar(T).view(1, 1, 1, T) ^ mul.unsqueeze(3), 0)
+    return h >= dropout_thresh(p)
+
+
+def _attn_drop(name, q, dropout, seed, seed_dev, store):
+    """(p, seed tensor for the kernels, seed value for the CPU path) of the
+    dropout arguments; p == 0: (0.0, None, None)"""
+    p = _f32(dropout)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("%s: dropout must be in [0, 1), got %r" %
+                         (name, dropout))
+    if p == 0.0:
+        return 0.0, None, None
+    if seed_dev is None and seed is None:
+        raise ValueError("%s: dropout needs seed or seed_dev" % name)
+    if seed_dev is not None and (
+            not isinstance(seed_dev, torch.Tensor) or seed_dev.numel() != 1
+            or seed_dev.dtype != torch.int32 or seed_dev.device != q.device):
+        raise ValueError("%s: seed_dev must be a 1-element int32 tensor on %s"
+                         % (name, q.device))
+    if not _gpu(q):
+        return p, None, (int(seed_dev.reshape(-1)[0]) if seed_dev is not None
+                         else int(seed)) & 0xFFFFFFFF
+    if seed_dev is None:
+        # a host seed: into a tensor the caller's dict keeps.  Not for a
+        # captured step, which would replay the value of the capture
+        v = int(seed) & 0xFFFFFFFF
+        seed_dev = _rec_buf(store, "seed", (1,), torch.int32, q.device)
+        seed_dev.fill_(v - (1 << 32) if v >= (1 << 31) else v)
+    return p, seed_dev, None
+
+
+def _attn_keep(B, NH, T, seed, p, base_row):
+    """float32 M / (1 - p) of the CPU path"""
+    keep = attention_dropout_mask_ref(B, NH, T, seed, p, base_row)
+    one = torch.ones((), dtype=torch.float32)
+    inv = one / (one - torch.tensor(p, dtype=torch.float32))
+    return keep.float() * inv
+
+
+def attention_fwd(q, k, v, heads, causal=False, out=None, save=None,
+                  dropout=0.0, seed=None, seed_dev=None, base_row=0):
     """Scaled dot-product self-attention over ``heads`` heads.
 
     ``q``, ``k``, ``v`` are [B][T][E] views with contiguous rows and a row
@@ -4155,7 +4211,15 @@ def attention_fwd(q, k, v, heads, causal=False, out=None, save=None):
 
     GPU: bfloat16 operands, ``hvk_attn_fwd`` (flash style: no [T][T] tensor
     in memory) on the current stream.  CPU: float32, S materialised per
-    (batch, head) with the row maximum subtracted."""
+    (batch, head) with the row maximum subtracted.
+
+    ``dropout`` = p in [0, 1): o = (P o M / (1 - p)) v with the keep mask of
+    :func:`attention_dropout_mask_ref`; lse stays that of the undropped
+    scores.  The seed is ``seed_dev`` (a 1-element int32 tensor on q's
+    device: graph-safe, see :func:`seed_advance`) or the host value ``seed``,
+    which on the GPU is uploaded into ``save["seed"]``.  ``base_row``: the
+    rank's first sample in the global minibatch.  GPU: ``hvk_adrop_fwd``.
+    p == 0 takes exactly the calls without these arguments."""
     name = "attention_fwd"
     B, T, E, ldq = _attn_view(name, "q", q)
     _attn_dtype(name, q)
@@ -4169,7 +4233,14 @@ def attention_fwd(q, k, v, heads, causal=False, out=None, save=None):
     _, _, _, ldo = _attn_view(name, "out", out, like=q)
     save = {} if save is None else save
     lse = _rec_buf(save, "lse", (B, NH, T), torch.float32, dev)
+    p, sd, sv = _attn_drop(name, q, dropout, seed, seed_dev, save)
     if _gpu(q):
+        if p:
+            _lib.check(_attn_fn("hvk_adrop_fwd")(
+                _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, _p(lse), B,
+                T, NH, D, int(bool(causal)), _p(sd), p, int(base_row),
+                _s(q)), "hvk_adrop_fwd")
+            return out
         _lib.check(_attn_fn("hvk_attn_fwd")(
             _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, _p(lse), B, T,
             NH, D, int(bool(causal)), _s(q)), "hvk_attn_fwd")
@@ -4182,13 +4253,17 @@ def attention_fwd(q, k, v, heads, causal=False, out=None, save=None):
     e = torch.exp(s - m)
     l = e.sum(dim=3, keepdim=True)
     lse.copy_((m + torch.log(l)).squeeze(3))
-    o = (e / l) @ vh
+    pr = e / l
+    if p:
+        pr = pr * _attn_keep(B, NH, T, sv, p, base_row)
+    o = pr @ vh
     out.copy_(o.permute(0, 2, 1, 3).reshape(B, T, E))
     return out
 
 
 def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
-                  dk=None, dv=None, ws=None):
+                  dk=None, dv=None, ws=None, dropout=0.0, seed=None,
+                  seed_dev=None, base_row=0):
     """Backward of :func:`attention_fwd` from its ``save`` ("lse"): returns
     (dq, dk, dv), each [B][T][E] (the given views, e.g. column slices of one
     fused gradient buffer, or new tensors).
@@ -4199,7 +4274,12 @@ def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
 
     GPU: ``hvk_attn_bwd_delta``, ``hvk_attn_bwd_dkv`` and ``hvk_attn_bwd_dq``
     (P recomputed from lse in both; no atomics, the result repeats bit for
-    bit); ``ws`` (a dict) keeps "delta".  CPU: float32."""
+    bit); ``ws`` (a dict) keeps "delta".  CPU: float32.
+
+    With ``dropout`` = p > 0 (the arguments of :func:`attention_fwd`, and
+    the seed VALUE the forward used): dV = P~^T dO and dP = (dO V^T) o M /
+    (1 - p) with P~ = P o M / (1 - p); delta is unchanged.  GPU:
+    ``hvk_adrop_bwd_dkv`` and ``hvk_adrop_bwd_dq``."""
     name = "attention_bwd"
     B, T, E, ldq = _attn_view(name, "q", q)
     _attn_dtype(name, q)
@@ -4223,11 +4303,22 @@ def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
     ws = {} if ws is None else ws
     delta = _rec_buf(ws, "delta", (B, NH, T), torch.float32, dev)
     c = int(bool(causal))
+    p, sd, sv = _attn_drop(name, q, dropout, seed, seed_dev, ws)
     if _gpu(q):
         s = _s(q)
         _lib.check(_attn_fn("hvk_attn_bwd_delta")(
             _p(do), lddo, _p(o), ldo, _p(delta), B, T, NH, D, s),
             "hvk_attn_bwd_delta")
+        if p:
+            tail = (B, T, NH, D, c, _p(sd), p, int(base_row), s)
+            _lib.check(_attn_fn("hvk_adrop_bwd_dkv")(
+                _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
+                _p(delta), _p(dk), lddk, _p(dv), lddv, *tail),
+                "hvk_adrop_bwd_dkv")
+            _lib.check(_attn_fn("hvk_adrop_bwd_dq")(
+                _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
+                _p(delta), _p(dq), lddq, *tail), "hvk_adrop_bwd_dq")
+            return dq, dk, dv
         _lib.check(_attn_fn("hvk_attn_bwd_dkv")(
             _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
             _p(delta), _p(dk), lddk, _p(dv), lddv, B, T, NH, D, c, s),
@@ -4239,14 +4330,18 @@ def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
     scale = 1.0 / math.sqrt(D)
     qh, kh, vh, oh, doh = (_attn_heads(t, NH, D) for t in (q, k, v, o, do))
     s = (qh @ kh.transpose(2, 3)) * scale
-    p = torch.exp(s - lse.unsqueeze(3))
+    pr = torch.exp(s - lse.unsqueeze(3))
     if causal:
-        p = p.masked_fill(_attn_mask(T, dev), 0.0)
+        pr = pr.masked_fill(_attn_mask(T, dev), 0.0)
     delta.copy_((doh * oh).sum(3))
     dp = doh @ vh.transpose(2, 3)
-    ds = p * (dp - delta.unsqueeze(3)) * scale
+    pd = pr
+    if p:
+        keep = _attn_keep(B, NH, T, sv, p, base_row)
+        pd, dp = pr * keep, dp * keep
+    ds = pr * (dp - delta.unsqueeze(3)) * scale
     for t, g in ((dq, ds @ kh), (dk, ds.transpose(2, 3) @ qh),
-                 (dv, p.transpose(2, 3) @ doh)):
+                 (dv, pd.transpose(2, 3) @ doh)):
         t.copy_(g.permute(0, 2, 1, 3).reshape(B, T, E))
     return dq, dk, dv
 
@@ -4310,7 +4405,8 @@ def _mha_rows(x, B, T):
 
 
 def mha_fwd(x, w_in, w_out, bias, heads, *, causal=False, save=None,
-            ws=None, out=None):
+            ws=None, out=None, dropout=0.0, seed=None, seed_dev=None,
+            base_row=0):
     """Multi-head self-attention layer over ``x`` [B][T][I] (batch-major):
     ``torch.nn.MultiheadAttention(E, heads, bias=True, batch_first=True)``
     applied to (x, x, x).
@@ -4324,7 +4420,9 @@ def mha_fwd(x, w_in, w_out, bias, heads, *, causal=False, save=None,
     ``save`` (a dict) receives "qkv" [B*T][3E], "o" [B][T][E] and "lse" for
     :func:`mha_bwd`; q, k and v are column slices of "qkv": no head
     transposes, no copies.  A kept ``save`` / ``ws`` dict is reused: no
-    allocation from the second call on."""
+    allocation from the second call on.  ``dropout``, ``seed``,
+    ``seed_dev``, ``base_row``: dropout on the attention weights, as in
+    :func:`attention_fwd` (torch's ``dropout=`` argument)."""
     name = "mha_fwd"
     B, T, I, E, D = _mha_args(name, x, w_in, w_out, bias, heads)
     dev = x.device
@@ -4349,7 +4447,8 @@ def mha_fwd(x, w_in, w_out, bias, heads, *, causal=False, save=None,
         qkv.copy_(r if b_in is None else r + b_in.float())
     q3 = qkv.view(B, T, 3 * E)
     attention_fwd(q3[:, :, :E], q3[:, :, E:2 * E], q3[:, :, 2 * E:], heads,
-                  causal=causal, out=o, save=st)
+                  causal=causal, out=o, save=st, dropout=dropout, seed=seed,
+                  seed_dev=seed_dev, base_row=base_row)
     if _gpu(x):
         gemm(o.view(B * T, E), w_out, trans_b=True, bias=b_out,
              out=out.view(B * T, E))
@@ -4361,9 +4460,11 @@ def mha_fwd(x, w_in, w_out, bias, heads, *, causal=False, save=None,
 
 def mha_bwd(err, x, w_in, w_out, save, dw_in, dw_out, dbias, heads, *,
             causal=False, accumulate="overwrite", need_err_input=True,
-            err_input=None, aux=None, aux_act=0):
+            err_input=None, aux=None, aux_act=0, dropout=0.0, seed=None,
+            seed_dev=None, base_row=0):
     """Backward of :func:`mha_fwd` from its ``save`` dict.  ``err`` is dL/dy
-    [B][T][E].
+    [B][T][E].  ``dropout``, ``seed``, ``seed_dev``, ``base_row``: those of
+    the forward, with the seed value it used.
 
         dw_out (+)= err^T o, dbias[3E:] (+)= its column sums (one GEMM)
         do = err w_out;  (dq | dk | dv) = attention_bwd, into one fused
@@ -4430,7 +4531,9 @@ def mha_bwd(err, x, w_in, w_out, save, dw_in, dw_out, dbias, heads, *,
     q3, g3 = save["qkv"].view(B, T, 3 * E), dqkv.view(B, T, 3 * E)
     attention_bwd(do, q3[:, :, :E], q3[:, :, E:2 * E], q3[:, :, 2 * E:],
                   save["o"], save, heads, causal=causal, dq=g3[:, :, :E],
-                  dk=g3[:, :, E:2 * E], dv=g3[:, :, 2 * E:], ws=save)
+                  dk=g3[:, :, E:2 * E], dv=g3[:, :, 2 * E:], ws=save,
+                  dropout=dropout, seed=seed, seed_dev=seed_dev,
+                  base_row=base_row)
     gemm(dqkv, x2, trans_a=True, out=dw_in, accumulate=accumulate,
          bias_grad=db_in)
     if not need_err_input:

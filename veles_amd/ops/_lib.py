@@ -195,6 +195,12 @@ _OPTIONAL = {
     "hvk_attn_bwd_delta": [P, L] * 2 + [P, I, I, I, I, P],
     "hvk_attn_bwd_dkv": [P, L] * 4 + [P, P] + [P, L] * 2 + [I, I, I, I, I, P],
     "hvk_attn_bwd_dq": [P, L] * 4 + [P, P] + [P, L] + [I, I, I, I, I, P],
+    # the same with dropout on P: (seed_dev, p, base_row) before the stream
+    "hvk_adrop_fwd": [P, L] * 4 + [P, I, I, I, I, I, P, F, L, P],
+    "hvk_adrop_bwd_dkv": [P, L] * 4 + [P, P] + [P, L] * 2 +
+                         [I, I, I, I, I, P, F, L, P],
+    "hvk_adrop_bwd_dq": [P, L] * 4 + [P, P] + [P, L] +
+                        [I, I, I, I, I, P, F, L, P],
     # layer normalisation and the residual add (csrc/kernels/layernorm.hip):
     # (P, C, vec); (x, ldx, C); (mode); (x, r, y each with its pitch, P, C,
     # gamma, beta, eps, mean, invstd, s); (err, x, r, dx each with its pitch,
