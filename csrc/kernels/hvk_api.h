@@ -116,6 +116,28 @@ int hvk_adrop_bwd_dq(const void* q, long long ldq, const void* k,
                      int T, int NH, int D, int causal,
                      const uint32_t* seed_dev, float p, long long base_row,
                      hipStream_t s);
+// grouped-query heads: k, v, dk, dv are [B][T][KVH*D], query head h reads K/V
+// head h / (NH / KVH); the mask row stays that of query head h of NH.
+// p == 0 with a null seed_dev: no dropout
+int hvk_gqa_fwd(const void* q, long long ldq, const void* k, long long ldk,
+                const void* v, long long ldv, void* o, long long ldo,
+                float* lse, int B, int T, int NH, int KVH, int D, int causal,
+                const uint32_t* seed_dev, float p, long long base_row,
+                hipStream_t s);
+int hvk_gqa_bwd_dkv(const void* q, long long ldq, const void* k,
+                    long long ldk, const void* v, long long ldv,
+                    const void* dout, long long lddo, const float* lse,
+                    const float* delta, void* dk, long long lddk, void* dv,
+                    long long lddv, int B, int T, int NH, int KVH, int D,
+                    int causal, const uint32_t* seed_dev, float p,
+                    long long base_row, hipStream_t s);
+int hvk_gqa_bwd_dq(const void* q, long long ldq, const void* k,
+                   long long ldk, const void* v, long long ldv,
+                   const void* dout, long long lddo, const float* lse,
+                   const float* delta, void* dq, long long lddq, int B, int T,
+                   int NH, int KVH, int D, int causal,
+                   const uint32_t* seed_dev, float p, long long base_row,
+                   hipStream_t s);
 int hvk_act_fwd(const void* x, int xdt, void* y, int ydt, long long n, int act,
                 hipStream_t s);
 int hvk_softmax_ce(const void* logits, int in_dt, int B, int C,

@@ -26,7 +26,16 @@ seed is advanced in every call, as the layer does) and (c) SDPA with
 ``dropout_p=P``; the summary is (d) - (a) against the two spreads, and
 (c) / (d).
 
-    python tools/bench_attention.py [--rounds 7] [--dropout P] [--out FILE]
+With ``--kv-heads G`` (grouped-query heads, G = NH / KVH query heads per K/V
+head) the variants are (a) the full-width kernels at KVH = NH (not the same
+computation: what sharing saves), (g) the grouped-query kernels (``hvk_gqa_*``)
+on q and the narrow k, v of one fused [B*T][E + 2 KVH D] buffer, and (e) what
+a user did without them: the full-width kernels on ``repeat_interleave``-d K/V
+plus the torch sum of dk / dv over the group; the summary is (e) - (g) against
+the two spreads.
+
+    python tools/bench_attention.py [--rounds 7] [--dropout P] [--kv-heads G]
+                                    [--out FILE]
 """
 import argparse
 import json
@@ -91,7 +100,48 @@ def graphed(fn):
         return None
 
 
-def variants(B, T, NH, D, causal, dev, drop=0.0):
+def gqa_variants(B, T, NH, D, causal, dev, G, gen, do, o):
+    """(g) and (e) of ``--kv-heads``: q and the narrow k, v are column slices
+    of one fused [B][T][E + 2 KVH D] buffer, the gradients of another"""
+    KVH = NH // G
+    E, EK = NH * D, KVH * D
+    qkv = torch.randn(B, T, E + 2 * EK, device=dev, generator=gen).bfloat16()
+    q, k, v = qkv[:, :, :E], qkv[:, :, E:E + EK], qkv[:, :, E + EK:]
+    dqkv = torch.empty_like(qkv)
+    dq, dk, dv = dqkv[:, :, :E], dqkv[:, :, E:E + EK], dqkv[:, :, E + EK:]
+    save, ws, esave, ews = {}, {}, {}, {}
+    wide = [torch.empty(B, T, E, dtype=torch.bfloat16, device=dev)
+            for _ in range(4)]             # k, v expanded; their gradients
+
+    def g_fwd():
+        ops.attention_fwd(q, k, v, NH, causal=causal, out=o, save=save,
+                          kv_heads=KVH)
+
+    def g_both():
+        g_fwd()
+        ops.attention_bwd(do, q, k, v, o, save, NH, causal=causal, dq=dq,
+                          dk=dk, dv=dv, ws=ws, kv_heads=KVH)
+
+    def e_fwd():
+        for t, w in ((k, wide[0]), (v, wide[1])):
+            w.view(B, T, KVH, G, D).copy_(t.view(B, T, KVH, 1, D).expand(
+                B, T, KVH, G, D))
+        ops.attention_fwd(q, wide[0], wide[1], NH, causal=causal, out=o,
+                          save=esave)
+
+    def e_both():
+        e_fwd()
+        ops.attention_bwd(do, q, wide[0], wide[1], o, esave, NH,
+                          causal=causal, dq=dq, dk=wide[2], dv=wide[3],
+                          ws=ews)
+        for t, w in ((dk, wide[2]), (dv, wide[3])):
+            torch.sum(w.view(B, T, KVH, G, D), 3,
+                      out=t.view(B, T, KVH, D))
+    return [("g fused gqa", g_fwd, g_both),
+            ("e expanded k, v", e_fwd, e_both)]
+
+
+def variants(B, T, NH, D, causal, dev, drop=0.0, group=0):
     E = NH * D
     gen = torch.Generator(device=dev).manual_seed(1)
     qkv = torch.randn(B, T, 3 * E, device=dev, generator=gen).bfloat16()
@@ -157,6 +207,8 @@ def variants(B, T, NH, D, causal, dev, drop=0.0):
             ("c torch sdpa", fwd_of(sdpa), both_of(sdpa))]
     if drop:
         rows[1] = ("d fused dropout", d_fwd, d_both)
+    if group:
+        rows[1:] = gqa_variants(B, T, NH, D, causal, dev, group, gen, do, o)
     for name, f, b in rows:
         for what, fn in (("fwd", f), ("fwd+bwd", b)):
             out.append(("%s %s eager" % (name, what), what, fn))
@@ -173,6 +225,10 @@ def main(argv=None):
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="compare the fused kernels at this drop "
                     "probability with p = 0 and with SDPA's dropout_p")
+    ap.add_argument("--kv-heads", type=int, default=0, metavar="G",
+                    help="grouped-query heads with KVH = NH / G at every "
+                    "shape: (g) hvk_gqa_* against (e) the full-width kernels "
+                    "on expanded K/V and (a) at KVH = NH")
     ap.add_argument("--shapes", default=None,
                     help="indices into SHAPES, e.g. 0,1")
     a = ap.parse_args(argv)
@@ -190,11 +246,15 @@ def main(argv=None):
     if a.dropout:
         say("dropout %g: (d) fused with dropout, (c) SDPA with dropout_p" %
             a.dropout)
+    if a.kv_heads:
+        say("grouped-query heads, KVH = NH / %d: (a) full width at KVH = NH, "
+            "(g) hvk_gqa_*, (e) full width on expanded K/V + group sums" %
+            a.kv_heads)
     shapes = SHAPES if a.shapes is None else \
         [SHAPES[int(i)] for i in a.shapes.split(",")]
     for B, T, NH, D in shapes:
         for causal in (False, True):
-            vs = variants(B, T, NH, D, causal, dev, a.dropout)
+            vs = variants(B, T, NH, D, causal, dev, a.dropout, a.kv_heads)
             flop = 4.0 * B * NH * T * T * D * (0.5 if causal else 1.0)
             calls = max(2, min(50, int(2e10 / flop)))
             times = {name: [] for name, _, _ in vs}
@@ -240,7 +300,21 @@ def main(argv=None):
                             rd["median_us"] / ra["median_us"],
                             "" if not rc else ", (c) / (d) = %.2f" % (
                                 rc["median_us"] / rd["median_us"])))
-            for mode in () if a.dropout else ("eager", "graph"):
+            for mode in ("eager", "graph") if a.kv_heads else ():
+                ra = med.get("a fused fwd+bwd " + mode)
+                rg = med.get("g fused gqa fwd+bwd " + mode)
+                re_ = med.get("e expanded k, v fwd+bwd " + mode)
+                if ra and rg and re_:
+                    spread = (rg["max_us"] - rg["min_us"]) + \
+                        (re_["max_us"] - re_["min_us"])
+                    gain = re_["median_us"] - rg["median_us"]
+                    say("  fwd+bwd %s: (e) - (g) = %.1f us, spreads added "
+                        "%.1f us: %s; (e) / (g) = %.2f, (a) / (g) = %.2f" % (
+                            mode, gain, spread,
+                            "accepted" if gain > spread else "NOT accepted",
+                            re_["median_us"] / rg["median_us"],
+                            ra["median_us"] / rg["median_us"]))
+            for mode in () if a.dropout or a.kv_heads else ("eager", "graph"):
                 ra = med.get("a fused fwd+bwd " + mode)
                 rb = med.get("b unfused torch fwd+bwd " + mode)
                 rc = med.get("c torch sdpa fwd+bwd " + mode)

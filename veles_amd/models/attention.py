@@ -29,6 +29,12 @@ draws a fresh mask every replay), a snapshot resumes the mask stream exactly,
 and rank r of a data-parallel run draws the rows of samples r B .. r B + B - 1
 of the global minibatch.  Identity when the workflow is testing and on
 non-TRAIN minibatches.
+
+Grouped-query heads: ``kv_heads`` = KVH (default ``heads``; it must divide
+``heads``; 1 is multi-query attention) projects KVH key / value heads, and
+query head h reads K/V head h // (NH / KVH).  W_in is then [E + 2 KVH D][I],
+rows q (E), k (KVH D), v (KVH D), ``weights`` has (E + 2 KVH D) I + E E
+values and ``bias`` is [E + 2 KVH D + E]; fan-ins and fills are unchanged.
 """
 from __future__ import annotations
 
@@ -57,6 +63,8 @@ class Attention(Forward):
             oss = oss[0]
         self.width = int(oss)
         self.heads = int(kwargs.get("heads", 1))
+        kvh = kwargs.get("kv_heads")
+        self.kv_heads = self.heads if kvh is None else int(kvh)
         self.causal = bool(kwargs.get("causal", False))
         self.dropout = float(kwargs.get("dropout", 0.0))
         if not 0.0 <= self.dropout < 1.0:
@@ -108,11 +116,17 @@ class Attention(Forward):
     def output_sample_shape(self):
         return (self.steps, self.width)
 
+    @property
+    def qkv_width(self):
+        """rows of W_in: E + 2 KVH D (3E without ``kv_heads``)"""
+        return self.width + 2 * self.kv_heads * (self.width // self.heads)
+
     def split(self, flat, n_in):
-        """(W_in [3E][I], W_o [E][E]) views of a flat weights-like tensor"""
-        E = self.width
-        n = 3 * E * n_in
-        return flat[:n].view(3 * E, n_in), flat[n:].view(E, E)
+        """(W_in [E + 2 KVH D][I], W_o [E][E]) views of a flat weights-like
+        tensor"""
+        E, W = self.width, self.qkv_width
+        n = W * n_in
+        return flat[:n].view(W, n_in), flat[n:].view(E, E)
 
     def initialize(self, device=None, **kwargs):
         super().initialize(device=device, **kwargs)
@@ -123,8 +137,10 @@ class Attention(Forward):
         B, self.steps, n_in = shape
         E = self.width
         ops.attn_head_dim(E, self.heads, self.name)
+        ops.attn_kv_heads(self.heads, self.kv_heads, self.name)
         self.n_in = n_in
-        n = 3 * E * n_in
+        W = self.qkv_width
+        n = W * n_in
         wshape = (n + E * E,)
         # created here, weights before bias as register_params would: the
         # two blocks have a fan-in each, and the biases start at 0
@@ -137,9 +153,9 @@ class Attention(Forward):
                              else self.weights_stddev, self.rand)
             self.weights.reset(w)
         if self.include_bias and (self.bias.mem is None or
-                                  self.bias.mem.shape != (4 * E,)):
-            self.bias.reset(numpy.zeros(4 * E, numpy.float32))
-        self.register_params(wshape, n_in, bias_len=4 * E)
+                                  self.bias.mem.shape != (W + E,)):
+            self.bias.reset(numpy.zeros(W + E, numpy.float32))
+        self.register_params(wshape, n_in, bias_len=W + E)
         self.save_ = {}
         self.alloc_output((B,) + self.output_sample_shape)
 
@@ -155,7 +171,8 @@ class Attention(Forward):
         self.drop_ = self.drop_args(x, testing)
         ops.mha_fwd(x, w_in, w_out, self.bias_master, self.heads,
                     causal=self.causal, save=None if testing else self.save_,
-                    ws=self.save_, out=y, **self.drop_)
+                    ws=self.save_, out=y, kv_heads=self.kv_heads,
+                    **self.drop_)
 
 
 class GDAttention(GradientDescentBase):
@@ -195,5 +212,6 @@ class GDAttention(GradientDescentBase):
                     None if pb is None else pb.grad, fwd.heads,
                     causal=fwd.causal, accumulate=mode,
                     need_err_input=self.need_err_input, err_input=ei,
-                    aux=aux, aux_act=aux_act, **fwd.drop_)
+                    aux=aux, aux_act=aux_act, kv_heads=fwd.kv_heads,
+                    **fwd.drop_)
         self.report_gradients()

@@ -35,6 +35,7 @@ __all__ = ["ACT", "gemm", "linear_fwd", "conv_out_size", "conv_fwd",
            "rbm_layout", "rbm_uniforms", "rbm_sample", "rbm_grad",
            "bn_partials", "batchnorm_fwd", "batchnorm_bwd", "attention_fwd",
            "attention_bwd", "mha_fwd", "mha_bwd", "attn_head_dim",
+           "attn_kv_heads",
            "attention_dropout_mask_ref",
            "ln_partials", "layernorm_fwd", "layernorm_bwd", "add",
            "FFN_ACT", "ffn_partials", "ffn_act_fwd", "ffn_act_bwd",
@@ -4081,9 +4082,21 @@ def attn_head_dim(E, heads, name="attention"):
     return D
 
 
-def _attn_view(name, what, t, like=None):
+def attn_kv_heads(heads, kv_heads, name="attention"):
+    """KVH of grouped-query attention: query head h reads K/V head h // G,
+    G = heads / KVH.  ``kv_heads`` None is ``heads`` (one K/V head per query
+    head); checked on every device, like :func:`attn_head_dim`"""
+    NH = int(heads)
+    KVH = NH if kv_heads is None else int(kv_heads)
+    if KVH < 1 or KVH > NH or NH % KVH:
+        raise ValueError("%s: kv_heads must divide heads = %d and lie in "
+                         "1 .. %d, got %r" % (name, NH, NH, kv_heads))
+    return KVH
+
+
+def _attn_view(name, what, t, like=None, width=None):
     """(B, T, E, pitch) of a [B][T][E] view with contiguous rows and one row
-    pitch over [B][T]"""
+    pitch over [B][T]; ``width``: E of a K/V-wide operand next to q's"""
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s: %s must be a tensor, got %s" % (
             name, what, type(t).__name__))
@@ -4099,9 +4112,13 @@ def _attn_view(name, what, t, like=None):
         raise ValueError("%s: %s spans %d x %d x %d elements, the limit is "
                          "2^31 - 1" % (name, what, B, T, ld))
     if like is not None:
-        if tuple(t.shape) != tuple(like.shape):
-            raise ValueError("%s: %s is %s, q is %s" % (
-                name, what, tuple(t.shape), tuple(like.shape)))
+        want = tuple(like.shape) if width is None else \
+            tuple(like.shape[:2]) + (width,)
+        if tuple(t.shape) != want:
+            raise ValueError("%s: %s is %s, q is %s%s" % (
+                name, what, tuple(t.shape), tuple(like.shape),
+                "" if width in (None, like.shape[2])
+                else " and K/V are %d wide" % width))
         if t.dtype != like.dtype:
             raise TypeError("%s: %s is %s, q is %s" % (
                 name, what, t.dtype, like.dtype))
@@ -4197,8 +4214,22 @@ def _attn_keep(B, NH, T, seed, p, base_row):
     return keep.float() * inv
 
 
+def _attn_group(t, G):
+    """K/V heads [B][KVH][T][D] -> the NH = KVH G query heads that read them"""
+    return t if G == 1 else t.repeat_interleave(G, dim=1)
+
+
+def _attn_group_sum(t, G):
+    """[B][NH][T][D] gradients of the expanded heads -> [B][KVH][T][D]"""
+    if G == 1:
+        return t
+    B, NH, T, D = t.shape
+    return t.reshape(B, NH // G, G, T, D).sum(2)
+
+
 def attention_fwd(q, k, v, heads, causal=False, out=None, save=None,
-                  dropout=0.0, seed=None, seed_dev=None, base_row=0):
+                  dropout=0.0, seed=None, seed_dev=None, base_row=0,
+                  kv_heads=None):
     """Scaled dot-product self-attention over ``heads`` heads.
 
     ``q``, ``k``, ``v`` are [B][T][E] views with contiguous rows and a row
@@ -4219,14 +4250,23 @@ def attention_fwd(q, k, v, heads, causal=False, out=None, save=None,
     device: graph-safe, see :func:`seed_advance`) or the host value ``seed``,
     which on the GPU is uploaded into ``save["seed"]``.  ``base_row``: the
     rank's first sample in the global minibatch.  GPU: ``hvk_adrop_fwd``.
-    p == 0 takes exactly the calls without these arguments."""
+    p == 0 takes exactly the calls without these arguments.
+
+    ``kv_heads`` = KVH < heads (grouped-query attention; KVH = 1 is
+    multi-query): ``k`` and ``v`` are [B][T][KVH*D] and query head h reads
+    K/V head h // G, G = heads / KVH (``repeat_interleave`` of the K/V
+    heads).  o, lse and the dropout mask stay per query head.  GPU:
+    ``hvk_gqa_fwd``, where a staged K/V tile serves the heads of its group.
+    None or ``heads`` takes exactly the calls without the argument."""
     name = "attention_fwd"
     B, T, E, ldq = _attn_view(name, "q", q)
     _attn_dtype(name, q)
-    _, _, _, ldk = _attn_view(name, "k", k, like=q)
-    _, _, _, ldv = _attn_view(name, "v", v, like=q)
     NH = int(heads)
     D = attn_head_dim(E, NH, name)
+    KVH = attn_kv_heads(NH, kv_heads, name)
+    G = NH // KVH
+    _, _, _, ldk = _attn_view(name, "k", k, like=q, width=KVH * D)
+    _, _, _, ldv = _attn_view(name, "v", v, like=q, width=KVH * D)
     dev = q.device
     if out is None:
         out = torch.empty(B, T, E, dtype=q.dtype, device=dev)
@@ -4235,6 +4275,12 @@ def attention_fwd(q, k, v, heads, causal=False, out=None, save=None,
     lse = _rec_buf(save, "lse", (B, NH, T), torch.float32, dev)
     p, sd, sv = _attn_drop(name, q, dropout, seed, seed_dev, save)
     if _gpu(q):
+        if G > 1:
+            _lib.check(_attn_fn("hvk_gqa_fwd")(
+                _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, _p(lse), B,
+                T, NH, KVH, D, int(bool(causal)), _p(sd), p, int(base_row),
+                _s(q)), "hvk_gqa_fwd")
+            return out
         if p:
             _lib.check(_attn_fn("hvk_adrop_fwd")(
                 _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, _p(lse), B,
@@ -4245,7 +4291,8 @@ def attention_fwd(q, k, v, heads, causal=False, out=None, save=None,
             _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, _p(lse), B, T,
             NH, D, int(bool(causal)), _s(q)), "hvk_attn_fwd")
         return out
-    qh, kh, vh = (_attn_heads(t, NH, D) for t in (q, k, v))
+    qh = _attn_heads(q, NH, D)
+    kh, vh = (_attn_group(_attn_heads(t, KVH, D), G) for t in (k, v))
     s = (qh @ kh.transpose(2, 3)) * (1.0 / math.sqrt(D))
     if causal:
         s = s.masked_fill(_attn_mask(T, dev), float("-inf"))
@@ -4263,7 +4310,7 @@ def attention_fwd(q, k, v, heads, causal=False, out=None, save=None,
 
 def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
                   dk=None, dv=None, ws=None, dropout=0.0, seed=None,
-                  seed_dev=None, base_row=0):
+                  seed_dev=None, base_row=0, kv_heads=None):
     """Backward of :func:`attention_fwd` from its ``save`` ("lse"): returns
     (dq, dk, dv), each [B][T][E] (the given views, e.g. column slices of one
     fused gradient buffer, or new tensors).
@@ -4279,26 +4326,34 @@ def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
     With ``dropout`` = p > 0 (the arguments of :func:`attention_fwd`, and
     the seed VALUE the forward used): dV = P~^T dO and dP = (dO V^T) o M /
     (1 - p) with P~ = P o M / (1 - p); delta is unchanged.  GPU:
-    ``hvk_adrop_bwd_dkv`` and ``hvk_adrop_bwd_dq``."""
+    ``hvk_adrop_bwd_dkv`` and ``hvk_adrop_bwd_dq``.
+
+    With ``kv_heads`` = KVH < heads (see :func:`attention_fwd`) k, v, dk and
+    dv are [B][T][KVH*D]; dk and dv of a K/V head are the sums over the
+    G = heads / KVH query heads that read it.  GPU: ``hvk_gqa_bwd_dkv`` adds
+    them up in its float32 accumulators, heads ascending, and rounds once;
+    ``hvk_gqa_bwd_dq``."""
     name = "attention_bwd"
     B, T, E, ldq = _attn_view(name, "q", q)
     _attn_dtype(name, q)
-    _, _, _, ldk = _attn_view(name, "k", k, like=q)
-    _, _, _, ldv = _attn_view(name, "v", v, like=q)
-    _, _, _, ldo = _attn_view(name, "o", o, like=q)
-    _, _, _, lddo = _attn_view(name, "do", do, like=q)
     NH = int(heads)
     D = attn_head_dim(E, NH, name)
+    KVH = attn_kv_heads(NH, kv_heads, name)
+    G, EK = NH // KVH, KVH * D
+    _, _, _, ldk = _attn_view(name, "k", k, like=q, width=EK)
+    _, _, _, ldv = _attn_view(name, "v", v, like=q, width=EK)
+    _, _, _, ldo = _attn_view(name, "o", o, like=q)
+    _, _, _, lddo = _attn_view(name, "do", do, like=q)
     dev = q.device
     if not isinstance(save, dict) or "lse" not in save:
         raise ValueError("%s: save must be attention_fwd's dict" % name)
     lse = save["lse"]
     _attn_stat(name, "save[\"lse\"]", lse, B, NH, T, dev)
     grads = []
-    for what, t in (("dq", dq), ("dk", dk), ("dv", dv)):
+    for what, t, w in (("dq", dq, E), ("dk", dk, EK), ("dv", dv, EK)):
         if t is None:
-            t = torch.empty(B, T, E, dtype=q.dtype, device=dev)
-        grads.append((t, _attn_view(name, what, t, like=q)[3]))
+            t = torch.empty(B, T, w, dtype=q.dtype, device=dev)
+        grads.append((t, _attn_view(name, what, t, like=q, width=w)[3]))
     (dq, lddq), (dk, lddk), (dv, lddv) = grads
     ws = {} if ws is None else ws
     delta = _rec_buf(ws, "delta", (B, NH, T), torch.float32, dev)
@@ -4309,6 +4364,16 @@ def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
         _lib.check(_attn_fn("hvk_attn_bwd_delta")(
             _p(do), lddo, _p(o), ldo, _p(delta), B, T, NH, D, s),
             "hvk_attn_bwd_delta")
+        if G > 1:
+            tail = (B, T, NH, KVH, D, c, _p(sd), p, int(base_row), s)
+            _lib.check(_attn_fn("hvk_gqa_bwd_dkv")(
+                _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
+                _p(delta), _p(dk), lddk, _p(dv), lddv, *tail),
+                "hvk_gqa_bwd_dkv")
+            _lib.check(_attn_fn("hvk_gqa_bwd_dq")(
+                _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
+                _p(delta), _p(dq), lddq, *tail), "hvk_gqa_bwd_dq")
+            return dq, dk, dv
         if p:
             tail = (B, T, NH, D, c, _p(sd), p, int(base_row), s)
             _lib.check(_attn_fn("hvk_adrop_bwd_dkv")(
@@ -4328,7 +4393,8 @@ def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
             _p(delta), _p(dq), lddq, B, T, NH, D, c, s), "hvk_attn_bwd_dq")
         return dq, dk, dv
     scale = 1.0 / math.sqrt(D)
-    qh, kh, vh, oh, doh = (_attn_heads(t, NH, D) for t in (q, k, v, o, do))
+    qh, oh, doh = (_attn_heads(t, NH, D) for t in (q, o, do))
+    kh, vh = (_attn_group(_attn_heads(t, KVH, D), G) for t in (k, v))
     s = (qh @ kh.transpose(2, 3)) * scale
     pr = torch.exp(s - lse.unsqueeze(3))
     if causal:
@@ -4340,14 +4406,16 @@ def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
         keep = _attn_keep(B, NH, T, sv, p, base_row)
         pd, dp = pr * keep, dp * keep
     ds = pr * (dp - delta.unsqueeze(3)) * scale
-    for t, g in ((dq, ds @ kh), (dk, ds.transpose(2, 3) @ qh),
-                 (dv, pd.transpose(2, 3) @ doh)):
-        t.copy_(g.permute(0, 2, 1, 3).reshape(B, T, E))
+    for t, g in ((dq, ds @ kh),
+                 (dk, _attn_group_sum(ds.transpose(2, 3) @ qh, G)),
+                 (dv, _attn_group_sum(pd.transpose(2, 3) @ doh, G))):
+        t.copy_(g.permute(0, 2, 1, 3).reshape(B, T, t.shape[2]))
     return dq, dk, dv
 
 
-def _mha_args(name, x, w_in, w_out, bias, heads):
-    """Shared host checks of mha_fwd / mha_bwd; returns (B, T, I, E, D)"""
+def _mha_args(name, x, w_in, w_out, bias, heads, kv_heads=None):
+    """Shared host checks of mha_fwd / mha_bwd; returns (B, T, I, E, EK) with
+    EK = kv_heads D the width of k and of v (E without ``kv_heads``)"""
     for what, t in (("x", x), ("w_in", w_in), ("w_out", w_out)):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s: %s must be a tensor, got %s" % (
@@ -4361,9 +4429,11 @@ def _mha_args(name, x, w_in, w_out, bias, heads):
                          (name, tuple(w_out.shape)))
     E = w_out.shape[0]
     D = attn_head_dim(E, heads, name)
-    if w_in.dim() != 2 or tuple(w_in.shape) != (3 * E, I):
+    EK = attn_kv_heads(heads, kv_heads, name) * D
+    W = E + 2 * EK
+    if w_in.dim() != 2 or tuple(w_in.shape) != (W, I):
         raise ValueError("%s: w_in must be [%d][%d] (rows q, k, v; E = %d, "
-                         "I = %d), got %s" % (name, 3 * E, I, E, I,
+                         "I = %d), got %s" % (name, W, I, E, I,
                                               tuple(w_in.shape)))
     if w_in.device != x.device or w_out.device != x.device or \
             (bias is not None and bias.device != x.device):
@@ -4375,10 +4445,10 @@ def _mha_args(name, x, w_in, w_out, bias, heads):
                          "over [B][T], weight rows contiguous (strides %s, "
                          "%s, %s)" % (name, x.stride(), w_in.stride(),
                                       w_out.stride()))
-    if bias is not None and (tuple(bias.shape) != (4 * E,) or
+    if bias is not None and (tuple(bias.shape) != (W + E,) or
                              not bias.is_contiguous()):
         raise ValueError("%s: bias must be a contiguous [%d] = (b_q, b_k, "
-                         "b_v, b_o), got %s" % (name, 4 * E,
+                         "b_v, b_o), got %s" % (name, W + E,
                                                 tuple(bias.shape)))
     if _gpu(x):
         if x.dtype != torch.bfloat16 or w_in.dtype != torch.bfloat16 or \
@@ -4393,10 +4463,10 @@ def _mha_args(name, x, w_in, w_out, bias, heads):
               w_out.is_floating_point()):
         raise TypeError("%s: floating-point operands, got %s / %s / %s" %
                         (name, x.dtype, w_in.dtype, w_out.dtype))
-    if B * T * max(3 * E, x.stride(1) if B * T > 1 else I) >= 1 << 31:
+    if B * T * max(W, x.stride(1) if B * T > 1 else I) >= 1 << 31:
         raise ValueError("%s: %d x %d x %d exceeds 2^31 elements" %
-                         (name, B, T, max(3 * E, I)))
-    return B, T, I, E, D
+                         (name, B, T, max(W, I)))
+    return B, T, I, E, EK
 
 
 def _mha_rows(x, B, T):
@@ -4406,7 +4476,7 @@ def _mha_rows(x, B, T):
 
 def mha_fwd(x, w_in, w_out, bias, heads, *, causal=False, save=None,
             ws=None, out=None, dropout=0.0, seed=None, seed_dev=None,
-            base_row=0):
+            base_row=0, kv_heads=None):
     """Multi-head self-attention layer over ``x`` [B][T][I] (batch-major):
     ``torch.nn.MultiheadAttention(E, heads, bias=True, batch_first=True)``
     applied to (x, x, x).
@@ -4422,9 +4492,14 @@ def mha_fwd(x, w_in, w_out, bias, heads, *, causal=False, save=None,
     transposes, no copies.  A kept ``save`` / ``ws`` dict is reused: no
     allocation from the second call on.  ``dropout``, ``seed``,
     ``seed_dev``, ``base_row``: dropout on the attention weights, as in
-    :func:`attention_fwd` (torch's ``dropout=`` argument)."""
+    :func:`attention_fwd` (torch's ``dropout=`` argument).
+
+    ``kv_heads`` = KVH < heads (grouped-query heads, :func:`attention_fwd`):
+    w_in is [E + 2 KVH D][I], rows q (E), k (KVH D), v (KVH D), bias
+    [E + 2 KVH D + E], and "qkv" [B*T][E + 2 KVH D]."""
     name = "mha_fwd"
-    B, T, I, E, D = _mha_args(name, x, w_in, w_out, bias, heads)
+    B, T, I, E, EK = _mha_args(name, x, w_in, w_out, bias, heads, kv_heads)
+    W = E + 2 * EK
     dev = x.device
     st = save if save is not None else (ws if ws is not None else {})
     dt = torch.bfloat16 if _gpu(x) else torch.float32
@@ -4435,20 +4510,20 @@ def mha_fwd(x, w_in, w_out, bias, heads, *, causal=False, save=None,
                          % (name, dt, B, T, E, dev))
     if out is None:
         out = torch.empty(B, T, E, dtype=dt, device=dev)
-    qkv = _rec_buf(st, "qkv", (B * T, 3 * E), dt, dev)
+    qkv = _rec_buf(st, "qkv", (B * T, W), dt, dev)
     o = _rec_buf(st, "o", (B, T, E), dt, dev)
-    b_in = None if bias is None else bias[:3 * E]
-    b_out = None if bias is None else bias[3 * E:]
+    b_in = None if bias is None else bias[:W]
+    b_out = None if bias is None else bias[W:]
     x2 = _mha_rows(x, B, T)
     if _gpu(x):
         gemm(x2, w_in, trans_b=True, bias=b_in, out=qkv)
     else:
         r = x2.float() @ w_in.float().t()
         qkv.copy_(r if b_in is None else r + b_in.float())
-    q3 = qkv.view(B, T, 3 * E)
-    attention_fwd(q3[:, :, :E], q3[:, :, E:2 * E], q3[:, :, 2 * E:], heads,
+    q3 = qkv.view(B, T, W)
+    attention_fwd(q3[:, :, :E], q3[:, :, E:E + EK], q3[:, :, E + EK:], heads,
                   causal=causal, out=o, save=st, dropout=dropout, seed=seed,
-                  seed_dev=seed_dev, base_row=base_row)
+                  seed_dev=seed_dev, base_row=base_row, kv_heads=kv_heads)
     if _gpu(x):
         gemm(o.view(B * T, E), w_out, trans_b=True, bias=b_out,
              out=out.view(B * T, E))
@@ -4461,7 +4536,7 @@ def mha_fwd(x, w_in, w_out, bias, heads, *, causal=False, save=None,
 def mha_bwd(err, x, w_in, w_out, save, dw_in, dw_out, dbias, heads, *,
             causal=False, accumulate="overwrite", need_err_input=True,
             err_input=None, aux=None, aux_act=0, dropout=0.0, seed=None,
-            seed_dev=None, base_row=0):
+            seed_dev=None, base_row=0, kv_heads=None):
     """Backward of :func:`mha_fwd` from its ``save`` dict.  ``err`` is dL/dy
     [B][T][E].  ``dropout``, ``seed``, ``seed_dev``, ``base_row``: those of
     the forward, with the seed value it used.
@@ -4475,9 +4550,12 @@ def mha_bwd(err, x, w_in, w_out, save, dw_in, dw_out, dbias, heads, *,
 
     ``dw_in`` float32 [3E][I], ``dw_out`` float32 [E][E], ``dbias`` float32
     [4E] or None; ``accumulate``: True adds, "overwrite" writes, as in
-    ``gemm``.  Returns err_input (None without ``need_err_input``)."""
+    ``gemm``.  Returns err_input (None without ``need_err_input``).  With
+    ``kv_heads`` = KVH < heads every 3E above is E + 2 KVH D and every 4E is
+    E + 2 KVH D + E, as in :func:`mha_fwd`."""
     name = "mha_bwd"
-    B, T, I, E, D = _mha_args(name, x, w_in, w_out, None, heads)
+    B, T, I, E, EK = _mha_args(name, x, w_in, w_out, None, heads, kv_heads)
+    W = E + 2 * EK
     dev = x.device
     gpu = _gpu(x)
     dt = torch.bfloat16 if gpu else torch.float32
@@ -4492,7 +4570,7 @@ def mha_bwd(err, x, w_in, w_out, save, dw_in, dw_out, dbias, heads, *,
     if gpu and err.dtype != torch.bfloat16:
         raise TypeError("%s: GPU err must be bfloat16, got %s" %
                         (name, err.dtype))
-    for what, t, shape in (("dw_in", dw_in, (3 * E, I)),
+    for what, t, shape in (("dw_in", dw_in, (W, I)),
                            ("dw_out", dw_out, (E, E))):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or \
                 tuple(t.shape) != shape or not t.is_contiguous() or \
@@ -4500,14 +4578,14 @@ def mha_bwd(err, x, w_in, w_out, save, dw_in, dw_out, dbias, heads, *,
             raise ValueError("%s: %s must be a contiguous float32 [%d][%d] "
                              "on %s" % (name, what, shape[0], shape[1], dev))
     if dbias is not None and (dbias.dtype != torch.float32 or
-                              tuple(dbias.shape) != (4 * E,) or
+                              tuple(dbias.shape) != (W + E,) or
                               not dbias.is_contiguous() or
                               dbias.device != dev):
         raise ValueError("%s: dbias must be a contiguous float32 [%d] on %s"
-                         % (name, 4 * E, dev))
+                         % (name, W + E, dev))
     NH = int(heads)
     _rec_save_check(name, "mha_fwd", save,
-                    (("qkv", (B * T, 3 * E), dt), ("o", (B, T, E), dt),
+                    (("qkv", (B * T, W), dt), ("o", (B, T, E), dt),
                      ("lse", (B, NH, T), torch.float32)), dev)
     aux_act = act_code(aux_act)
     if aux_act and aux is None:
@@ -4521,19 +4599,19 @@ def mha_bwd(err, x, w_in, w_out, save, dw_in, dw_out, dbias, heads, *,
     o2 = save["o"].view(B * T, E)
     x2 = _mha_rows(x, B, T) if gpu else _mha_rows(x, B, T).float()
     wi, wo = (w_in, w_out) if gpu else (w_in.float(), w_out.float())
-    db_in = None if dbias is None else dbias[:3 * E]
-    db_out = None if dbias is None else dbias[3 * E:]
+    db_in = None if dbias is None else dbias[:W]
+    db_out = None if dbias is None else dbias[W:]
     gemm(err2, o2, trans_a=True, out=dw_out, accumulate=accumulate,
          bias_grad=db_out)
     do = _rec_buf(save, "do", (B, T, E), dt, dev)
     gemm(err2, wo, out=do.view(B * T, E))
-    dqkv = _rec_buf(save, "dqkv", (B * T, 3 * E), dt, dev)
-    q3, g3 = save["qkv"].view(B, T, 3 * E), dqkv.view(B, T, 3 * E)
-    attention_bwd(do, q3[:, :, :E], q3[:, :, E:2 * E], q3[:, :, 2 * E:],
+    dqkv = _rec_buf(save, "dqkv", (B * T, W), dt, dev)
+    q3, g3 = save["qkv"].view(B, T, W), dqkv.view(B, T, W)
+    attention_bwd(do, q3[:, :, :E], q3[:, :, E:E + EK], q3[:, :, E + EK:],
                   save["o"], save, heads, causal=causal, dq=g3[:, :, :E],
-                  dk=g3[:, :, E:2 * E], dv=g3[:, :, 2 * E:], ws=save,
+                  dk=g3[:, :, E:E + EK], dv=g3[:, :, E + EK:], ws=save,
                   dropout=dropout, seed=seed, seed_dev=seed_dev,
-                  base_row=base_row)
+                  base_row=base_row, kv_heads=kv_heads)
     gemm(dqkv, x2, trans_a=True, out=dw_in, accumulate=accumulate,
          bias_grad=db_in)
     if not need_err_input:

@@ -201,6 +201,13 @@ _OPTIONAL = {
                          [I, I, I, I, I, P, F, L, P],
     "hvk_adrop_bwd_dq": [P, L] * 4 + [P, P] + [P, L] +
                         [I, I, I, I, I, P, F, L, P],
+    # grouped-query heads: k, v, dk, dv are [B][T][KVH*D]; (.., B, T, NH, KVH,
+    # D, causal, seed_dev, p, base_row, s), p == 0 with a null seed: no dropout
+    "hvk_gqa_fwd": [P, L] * 4 + [P, I, I, I, I, I, I, P, F, L, P],
+    "hvk_gqa_bwd_dkv": [P, L] * 4 + [P, P] + [P, L] * 2 +
+                       [I, I, I, I, I, I, P, F, L, P],
+    "hvk_gqa_bwd_dq": [P, L] * 4 + [P, P] + [P, L] +
+                      [I, I, I, I, I, I, P, F, L, P],
     # layer normalisation and the residual add (csrc/kernels/layernorm.hip):
     # (P, C, vec); (x, ldx, C); (mode); (x, r, y each with its pitch, P, C,
     # gamma, beta, eps, mean, invstd, s); (err, x, r, dx each with its pitch,
