@@ -5,19 +5,29 @@
 //   hvk_attn_bwd_delta  delta = rowsum(do * o)
 //   hvk_attn_bwd_dkv    dk, dv: a workgroup owns 128 keys, sweeps the queries
 //   hvk_attn_bwd_dq     dq:     a workgroup owns 128 queries, sweeps the keys
-//   hvk_gqa_fwd / _bwd_dkv / _bwd_dq   the same with G query heads per K/V
-//                       head ("grouped-query heads" below)
+//   hvk_adrop_fwd / _bwd_dkv / _bwd_dq  the same with dropout on P
+//   hvk_gqa_fwd / _bwd_dkv / _bwd_dq    the same with G query heads per K/V
+//                       head, with or without dropout
+//
+// There is ONE kernel source per pass (attn_fwd_kernel, attn_dq_kernel,
+// attn_dkv_kernel; attn_delta_kernel beside them) and one launcher per pass
+// (at_fwd, at_bwd_dkv, at_bwd_dq).  They are written for NH query heads over
+// KVH K/V heads; the hvk_attn_* and hvk_adrop_* entries pass KVH = NH.  The
+// tile body is written once; the GROUPED template flag selects only which
+// rows a workgroup owns ("the flash passes" below).
 //
 // Operands are [B][T][NH*D] bf16 views with a row pitch each (head h at
-// columns h*D ..), lse / delta are float32 [B][NH][T].  D is 32, 64 or 128.
+// columns h*D ..; k, v, dk, dv are [B][T][KVH*D]), lse / delta are float32
+// [B][NH][T].  D is 32, 64 or 128.
 //
-// Tiling.  A workgroup is 4 waves and owns AT_OWN = 128 rows (queries in
-// fwd / dq, keys in dkv) of one (batch, head), 32 per wave, ONE ROW PER LANE
-// PAIR (lane & 31; the lane halves split the other index).  It sweeps the
-// other index in tiles of AT_SWEEP = 32 rows that all four waves read from
-// one LDS copy.  The first product of a tile is oriented so that the swept
-// index is the accumulator's row (its 16 registers) and the owned row its
-// column (the lane):
+// Tiling.  A workgroup is 4 waves of 32 owned rows each (queries in fwd /
+// dq, keys in dkv), ONE ROW PER LANE PAIR (lane & 31; the lane halves split
+// the other index): with one query head per K/V head these are AT_OWN = 128
+// consecutive rows of one (batch, head).  It sweeps the other index in tiles
+// of AT_SWEEP = 32 rows that all four waves read from one LDS copy.  The
+// first product of a tile is oriented so that the swept index is the
+// accumulator's row (its 16 registers) and the owned row its column (the
+// lane):
 //   fwd, dq:  S^T = K Q^T, dP^T = V dO^T      (query on the lane)
 //   dkv:      S = Q K^T,   dP = dO V^T        (key on the lane)
 // so the softmax statistics (fwd) and lse / delta (dq) are lane-local, and
@@ -38,17 +48,17 @@
 // no atomics and no workgroup waiting for another, so results repeat bit for
 // bit (docs/OPS.md "Attention").
 //
-// Dropout on P (the DROP template flag; hvk_adrop_*): P~ = P o M / (1 - p)
-// feeds the second products, the softmax statistics stay those of P.  The mask
-// is counter-based, two hashes deep: row_seed = hash32(((base_row + b) NH + h)
-// T + i, seed), M_ij = hash32(j, row_seed) >= thresh, so no index grows with
-// T^2.  fwd and dq hold the query on the lane and hash the row once per lane
-// before the sweep; dkv sweeps the queries, so the 32 row seeds of a tile go
-// to LDS at staging.  Dropped elements are selected to +0 before the bf16
-// packing; 1 / (1 - p) multiplies o and dV at the store and dP in float32
-// right after its product.  The seed is read from device memory, so a
-// captured launch carries no host value.  DROP = false is the code without
-// any of this.
+// Dropout on P (the DROP template flag; hvk_adrop_*, hvk_gqa_* with a seed):
+// P~ = P o M / (1 - p) feeds the second products, the softmax statistics
+// stay those of P.  The mask is counter-based, two hashes deep: row_seed =
+// hash32(((base_row + b) NH + h) T + i, seed), M_ij = hash32(j, row_seed) >=
+// thresh, so no index grows with T^2.  fwd and dq hold the query on the lane
+// and hash the row once per lane before the sweep; dkv sweeps the queries, so
+// the 32 row seeds of a tile go to LDS at staging.  Dropped elements are
+// selected to +0 before the bf16 packing; 1 / (1 - p) multiplies o and dV at
+// the store and dP in float32 right after its product.  The seed is read
+// from device memory, so a captured launch carries no host value.  DROP =
+// false is the code without any of this.
 //
 // Masking: rows past T are loaded from the clamped row T-1 and masked to an
 // exact 0 in P; stores are guarded.  Every query row sees key 0 in the first
@@ -184,8 +194,9 @@ __device__ __forceinline__ uint32_t at_rowseed(const AtDrop& dr, int b, int h,
                        (uint32_t)T + (uint32_t)i, seed);
 }
 
+// the 128-row tile and the (batch, head) of a workgroup
 struct AtIds {
-  int tile, b, h, bh;
+  int tile, b, h;
 };
 // later_first: under the causal mask the later query tiles carry more work
 // (fwd, dq), so they are launched first
@@ -194,9 +205,9 @@ __device__ __forceinline__ AtIds at_ids(int ntiles, int NH, bool later_first) {
   const int bid = blockIdx.x;
   const int t = bid % ntiles;
   a.tile = later_first ? ntiles - 1 - t : t;
-  a.bh = bid / ntiles;
-  a.h = a.bh % NH;
-  a.b = a.bh / NH;
+  const int bh = bid / ntiles;
+  a.h = bh % NH;
+  a.b = bh / NH;
   return a;
 }
 
@@ -212,103 +223,6 @@ __device__ __forceinline__ void at_store_t(uint16_t* __restrict__ dst,
       at_st4<VEC>(dst + (long long)row * ld + db * 32 + 8 * g + 4 * hh,
                   acc[db][4 * g] * mul, acc[db][4 * g + 1] * mul,
                   acc[db][4 * g + 2] * mul, acc[db][4 * g + 3] * mul);
-}
-
-// ---------------------------------------------------------------- forward
-template <int D, bool VEC, bool DROP>
-__global__ void __launch_bounds__(AT_THREADS)
-attn_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
-                const uint16_t* __restrict__ k, long long ldk,
-                const uint16_t* __restrict__ v, long long ldv,
-                uint16_t* __restrict__ o, long long ldo,
-                float* __restrict__ lse, int T, int NH, int ntiles, int causal,
-                float c2, AtDrop dr) {
-  __shared__ __attribute__((aligned(16))) uint16_t kimg[32 * D];
-  __shared__ __attribute__((aligned(16))) uint16_t vtimg[D * AT_TRP];
-  const AtIds id = at_ids(ntiles, NH, true);
-  const long long row0 = (long long)id.b * T;
-  q += row0 * ldq + id.h * D;
-  k += row0 * ldk + id.h * D;
-  v += row0 * ldv + id.h * D;
-  o += row0 * ldo + id.h * D;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = lane & 31, hh = lane >> 5;
-  const int q0 = id.tile * AT_OWN, wq0 = q0 + 32 * w, qi = wq0 + r;
-  const bool wave_on = wq0 < T;
-  const int qc = min(qi, T - 1);
-  bf16x8 qf[D / 16];
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s)
-    qf[s] = __builtin_bit_cast(
-        bf16x8, at_ld8<VEC>(q + (long long)qc * ldq + 16 * s + 8 * hh));
-  f32x16 oacc[D / 32];
-#pragma unroll
-  for (int db = 0; db < D / 32; ++db) oacc[db] = at_zero();
-  float m = -INFINITY, l = 0.f;
-  uint32_t rseed = 0;
-  if constexpr (DROP)
-    rseed = at_rowseed(dr, id.b, id.h, NH, T, qi,
-                       __builtin_amdgcn_readfirstlane(dr.seed[0]));
-  const int klast = causal ? min(T - 1, q0 + AT_OWN - 1) : T - 1;
-  const int nkt = klast / AT_SWEEP + 1;
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int k0 = kt * AT_SWEEP;
-    if (kt) __syncthreads();
-    at_stage<D, VEC, true, false>(k, ldk, k0, T, kimg, nullptr);
-    at_stage<D, VEC, false, true>(v, ldv, k0, T, nullptr, vtimg);
-    __syncthreads();
-    if (!wave_on || (causal && k0 > wq0)) continue;   // wave-uniform
-    f32x16 sacc = at_zero();
-#pragma unroll
-    for (int s = 0; s < D / 16; ++s)
-      sacc = at_mfma(at_rowfrag<D>(kimg, r, 2 * s + hh), qf[s], sacc);
-    const bool edge = k0 + AT_SWEEP > T || (causal && k0 == wq0);
-    float p[16];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      float sv = sacc[i] * c2;
-      if (edge) {
-        const int key = k0 + at_accrow(i, hh);
-        if (key >= T || (causal && key > qi)) sv = -INFINITY;
-      }
-      p[i] = sv;
-      mx = fmaxf(mx, sv);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mn = fmaxf(m, mx);
-    const float alpha = __builtin_amdgcn_exp2f(m - mn);
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      p[i] = __builtin_amdgcn_exp2f(p[i] - mn);
-      sum += p[i];
-    }
-    sum += __shfl_xor(sum, 32, 64);
-    l = l * alpha + sum;
-    m = mn;
-#pragma unroll
-    for (int db = 0; db < D / 32; ++db)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) oacc[db][i] *= alpha;
-    if constexpr (DROP) {   // l took the undropped exponentials
-#pragma unroll
-      for (int i = 0; i < 16; ++i)
-        if (at_hash32((uint32_t)(k0 + at_accrow(i, hh)), rseed) < dr.thresh)
-          p[i] = 0.f;
-    }
-    const bf16x8 pb[2] = {at_pack8(p), at_pack8(p + 8)};
-#pragma unroll
-    for (int db = 0; db < D / 32; ++db)
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-        oacc[db] = at_mfma(at_trfrag(vtimg, db * 32 + r, 2 * s + hh), pb[s],
-                           oacc[db]);
-  }
-  if (wave_on && qi < T) {
-    at_store_t<D, VEC>(o, ldo, qi, hh, oacc, DROP ? dr.inv / l : 1.f / l);
-    if (hh == 0) lse[(long long)id.bh * T + qi] = m * AT_LN2 + logf(l);
-  }
 }
 
 // ------------------------------------------------------------------ delta
@@ -345,218 +259,48 @@ attn_delta_kernel(const uint16_t* __restrict__ dout, long long lddo,
   }
 }
 
-// --------------------------------------------------------------------- dq
-template <int D, bool VEC, bool DROP>
-__global__ void __launch_bounds__(AT_THREADS)
-attn_dq_kernel(const uint16_t* __restrict__ q, long long ldq,
-               const uint16_t* __restrict__ k, long long ldk,
-               const uint16_t* __restrict__ v, long long ldv,
-               const uint16_t* __restrict__ dout, long long lddo,
-               const float* __restrict__ lse, const float* __restrict__ delta,
-               uint16_t* __restrict__ dq, long long lddq, int T, int NH,
-               int ntiles, int causal, float c2, float scale, AtDrop dr) {
-  __shared__ __attribute__((aligned(16))) uint16_t kimg[32 * D];
-  __shared__ __attribute__((aligned(16))) uint16_t vimg[32 * D];
-  __shared__ __attribute__((aligned(16))) uint16_t ktimg[D * AT_TRP];
-  const AtIds id = at_ids(ntiles, NH, true);
-  const long long row0 = (long long)id.b * T;
-  q += row0 * ldq + id.h * D;
-  k += row0 * ldk + id.h * D;
-  v += row0 * ldv + id.h * D;
-  dout += row0 * lddo + id.h * D;
-  dq += row0 * lddq + id.h * D;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = lane & 31, hh = lane >> 5;
-  const int q0 = id.tile * AT_OWN, wq0 = q0 + 32 * w, qi = wq0 + r;
-  const bool wave_on = wq0 < T;
-  const int qc = min(qi, T - 1);
-  bf16x8 qf[D / 16], dof[D / 16];
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    qf[s] = __builtin_bit_cast(
-        bf16x8, at_ld8<VEC>(q + (long long)qc * ldq + 16 * s + 8 * hh));
-    dof[s] = __builtin_bit_cast(
-        bf16x8, at_ld8<VEC>(dout + (long long)qc * lddo + 16 * s + 8 * hh));
-  }
-  const float lse2 = lse[(long long)id.bh * T + qc] * AT_LOG2E;
-  const float dl = delta[(long long)id.bh * T + qc];
-  uint32_t rseed = 0;
-  if constexpr (DROP)
-    rseed = at_rowseed(dr, id.b, id.h, NH, T, qi,
-                       __builtin_amdgcn_readfirstlane(dr.seed[0]));
-  f32x16 acc[D / 32];
-#pragma unroll
-  for (int db = 0; db < D / 32; ++db) acc[db] = at_zero();
-  const int klast = causal ? min(T - 1, q0 + AT_OWN - 1) : T - 1;
-  const int nkt = klast / AT_SWEEP + 1;
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int k0 = kt * AT_SWEEP;
-    if (kt) __syncthreads();
-    at_stage<D, VEC, true, true>(k, ldk, k0, T, kimg, ktimg);
-    at_stage<D, VEC, true, false>(v, ldv, k0, T, vimg, nullptr);
-    __syncthreads();
-    if (!wave_on || (causal && k0 > wq0)) continue;   // wave-uniform
-    f32x16 sacc = at_zero(), pacc = at_zero();
-#pragma unroll
-    for (int s = 0; s < D / 16; ++s) {
-      sacc = at_mfma(at_rowfrag<D>(kimg, r, 2 * s + hh), qf[s], sacc);
-      pacc = at_mfma(at_rowfrag<D>(vimg, r, 2 * s + hh), dof[s], pacc);
-    }
-    const bool edge = k0 + AT_SWEEP > T || (causal && k0 == wq0);
-    float ds[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      float pv = __builtin_amdgcn_exp2f(sacc[i] * c2 - lse2);
-      if (edge) {
-        const int key = k0 + at_accrow(i, hh);
-        if (key >= T || (causal && key > qi)) pv = 0.f;
-      }
-      float dp = pacc[i];
-      if constexpr (DROP)
-        dp = at_hash32((uint32_t)(k0 + at_accrow(i, hh)), rseed) >= dr.thresh
-                 ? dp * dr.inv : 0.f;
-      ds[i] = pv * (dp - dl) * scale;
-    }
-    const bf16x8 dsb[2] = {at_pack8(ds), at_pack8(ds + 8)};
-#pragma unroll
-    for (int db = 0; db < D / 32; ++db)
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-        acc[db] = at_mfma(at_trfrag(ktimg, db * 32 + r, 2 * s + hh), dsb[s],
-                          acc[db]);
-  }
-  if (wave_on && qi < T) at_store_t<D, VEC>(dq, lddq, qi, hh, acc, 1.f);
-}
-
-// -------------------------------------------------------------------- dkv
-template <int D, bool VEC, bool DROP>
-__global__ void __launch_bounds__(AT_THREADS)
-attn_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
-                const uint16_t* __restrict__ k, long long ldk,
-                const uint16_t* __restrict__ v, long long ldv,
-                const uint16_t* __restrict__ dout, long long lddo,
-                const float* __restrict__ lse, const float* __restrict__ delta,
-                uint16_t* __restrict__ dk, long long lddk,
-                uint16_t* __restrict__ dv, long long lddv, int T, int NH,
-                int ntiles, int causal, float c2, float scale, AtDrop dr) {
-  __shared__ __attribute__((aligned(16))) uint16_t qimg[32 * D];
-  __shared__ __attribute__((aligned(16))) uint16_t doimg[32 * D];
-  __shared__ __attribute__((aligned(16))) uint16_t qtimg[D * AT_TRP];
-  __shared__ __attribute__((aligned(16))) uint16_t dotimg[D * AT_TRP];
-  __shared__ float rowc[2][AT_SWEEP];   // lse * log2(e), delta of the tile
-  __shared__ uint32_t rowsd[DROP ? AT_SWEEP : 1];   // mask row seeds of it
-  const AtIds id = at_ids(ntiles, NH, false);
-  const long long row0 = (long long)id.b * T;
-  q += row0 * ldq + id.h * D;
-  k += row0 * ldk + id.h * D;
-  v += row0 * ldv + id.h * D;
-  dout += row0 * lddo + id.h * D;
-  dk += row0 * lddk + id.h * D;
-  dv += row0 * lddv + id.h * D;
-  lse += (long long)id.bh * T;
-  delta += (long long)id.bh * T;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = lane & 31, hh = lane >> 5;
-  const int kb0 = id.tile * AT_OWN, wk0 = kb0 + 32 * w, kj = wk0 + r;
-  const bool wave_on = wk0 < T;
-  const int kc = min(kj, T - 1);
-  bf16x8 kf[D / 16], vf[D / 16];
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    kf[s] = __builtin_bit_cast(
-        bf16x8, at_ld8<VEC>(k + (long long)kc * ldk + 16 * s + 8 * hh));
-    vf[s] = __builtin_bit_cast(
-        bf16x8, at_ld8<VEC>(v + (long long)kc * ldv + 16 * s + 8 * hh));
-  }
-  uint32_t seed = 0;
-  if constexpr (DROP) seed = __builtin_amdgcn_readfirstlane(dr.seed[0]);
-  f32x16 dkacc[D / 32], dvacc[D / 32];
-#pragma unroll
-  for (int db = 0; db < D / 32; ++db) dkacc[db] = dvacc[db] = at_zero();
-  const int nqt = (T - 1) / AT_SWEEP + 1;
-  const int qt_first = causal ? kb0 / AT_SWEEP : 0;
-  for (int qt = qt_first; qt < nqt; ++qt) {
-    const int qt0 = qt * AT_SWEEP;
-    if (qt != qt_first) __syncthreads();
-    at_stage<D, VEC, true, true>(q, ldq, qt0, T, qimg, qtimg);
-    at_stage<D, VEC, true, true>(dout, lddo, qt0, T, doimg, dotimg);
-    if (threadIdx.x < 2 * AT_SWEEP) {
-      const int t = min(qt0 + (int)(threadIdx.x & 31), T - 1);
-      rowc[threadIdx.x >> 5][threadIdx.x & 31] =
-          threadIdx.x < AT_SWEEP ? lse[t] * AT_LOG2E : delta[t];
-    }
-    if constexpr (DROP) {   // in wave 1: wave 0 loads rowc
-      if (threadIdx.x >= 3 * AT_SWEEP && threadIdx.x < 4 * AT_SWEEP)
-        rowsd[threadIdx.x & 31] = at_rowseed(
-            dr, id.b, id.h, NH, T, qt0 + (int)(threadIdx.x & 31), seed);
-    }
-    __syncthreads();
-    if (!wave_on || (causal && qt0 < wk0)) continue;   // wave-uniform
-    f32x16 sacc = at_zero(), pacc = at_zero();
-#pragma unroll
-    for (int s = 0; s < D / 16; ++s) {
-      sacc = at_mfma(at_rowfrag<D>(qimg, r, 2 * s + hh), kf[s], sacc);
-      pacc = at_mfma(at_rowfrag<D>(doimg, r, 2 * s + hh), vf[s], pacc);
-    }
-    const bool edge = qt0 + AT_SWEEP > T || wk0 + 32 > T ||
-                      (causal && qt0 == wk0);
-    float p[16], ds[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int qr = at_accrow(i, hh);
-      float pv = __builtin_amdgcn_exp2f(sacc[i] * c2 - rowc[0][qr]);
-      if (edge) {
-        const int qrow = qt0 + qr;
-        if (qrow >= T || kj >= T || (causal && kj > qrow)) pv = 0.f;
-      }
-      float dp = pacc[i];
-      if constexpr (DROP) {
-        const bool keep = at_hash32((uint32_t)kj, rowsd[qr]) >= dr.thresh;
-        p[i] = keep ? pv : 0.f;
-        dp = keep ? dp * dr.inv : 0.f;
-      } else {
-        p[i] = pv;
-      }
-      ds[i] = pv * (dp - rowc[1][qr]) * scale;
-    }
-    const bf16x8 pb[2] = {at_pack8(p), at_pack8(p + 8)};
-    const bf16x8 dsb[2] = {at_pack8(ds), at_pack8(ds + 8)};
-#pragma unroll
-    for (int db = 0; db < D / 32; ++db)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        dvacc[db] = at_mfma(at_trfrag(dotimg, db * 32 + r, 2 * s + hh), pb[s],
-                            dvacc[db]);
-        dkacc[db] = at_mfma(at_trfrag(qtimg, db * 32 + r, 2 * s + hh), dsb[s],
-                            dkacc[db]);
-      }
-  }
-  if (wave_on && kj < T) {
-    at_store_t<D, VEC>(dk, lddk, kj, hh, dkacc, 1.f);
-    at_store_t<D, VEC>(dv, lddv, kj, hh, dvacc, DROP ? dr.inv : 1.f);
-  }
-}
-
-// ------------------------------------------------- grouped-query heads
-// hvk_gqa_*: G = NH / KVH query heads h = c G + g share K/V head c; k, v, dk
-// and dv are [B][T][KVH*D].  A K/V tile staged in LDS once serves every head
-// of the group the workgroup holds.
+// ------------------------------------------------------- the flash passes
+// One kernel source per pass serves plain and grouped-query heads: G = NH /
+// KVH query heads h = c G + g share K/V head c; k, v, dk and dv are
+// [B][T][KVH*D].  A K/V tile staged in LDS once serves every head of the
+// group the workgroup holds.  The GROUPED template flag selects nothing but
+// which rows a workgroup owns: at_gq or at_plain in fwd and dq, the bound of
+// the g loop in dkv.  hvk_gqa_* launch GROUPED = true; hvk_attn_* and
+// hvk_adrop_* launch GROUPED = false with KVH = NH (G = 1, c = h), where both
+// geometries are the same and give the same bits (docs/OPS.md "One kernel
+// source per pass" has why the flag is there).
 //
-// fwd, dq.  The owned unit stays a wave's 32 query rows.  The (32-row query
-// block, g) pairs of one (batch, c), block-major and g-minor, are cut into
-// workgroups of four consecutive slots, one per wave: the four waves sit at
-// (nearly) the same query rows of different heads, so under the causal mask
-// they need (nearly) the same key range, and at G = 4, T <= 32 they are the
-// four heads.  The sweep ends at the last key any slot of the workgroup
+// fwd, dq, GROUPED.  The owned unit is a wave's 32 query rows.  The (32-row
+// query block, g) pairs of one (batch, c), block-major and g-minor, are cut
+// into workgroups of four consecutive slots, one per wave: the four waves sit
+// at (nearly) the same query rows of different heads, so under the causal
+// mask they need (nearly) the same key range, and at G = 4, T <= 32 they are
+// the four heads.  The sweep ends at the last key any slot of the workgroup
 // needs; a wave skips the tiles past its own block.  Each wave carries its
 // own h for q / o / do, for its lse / delta row and for its mask row seed.
-struct AtGq {
+//
+// What a wave of fwd / dq owns: batch, K/V head c, query head h, its first
+// query row; whether it has rows at all; the last key of the workgroup's sweep
+struct AtOwn {
   int b, c, h, wq0, klast;
   bool on;
 };
-__device__ __forceinline__ AtGq at_gq(int nwg, int nslots, int KVH, int G,
+// not GROUPED: the four waves own the 128 query rows of tile nwg - 1 - t of
+// one (batch, head)
+__device__ __forceinline__ AtOwn at_plain(int nwg, int NH, int T, int causal) {
+  const AtIds i = at_ids(nwg, NH, true);
+  AtOwn a;
+  a.b = i.b;
+  a.c = a.h = i.h;
+  const int q0 = i.tile * AT_OWN;
+  a.wq0 = q0 + 32 * (int)(threadIdx.x >> 6);
+  a.on = a.wq0 < T;
+  a.klast = causal ? min(T - 1, q0 + AT_OWN - 1) : T - 1;
+  return a;
+}
+__device__ __forceinline__ AtOwn at_gq(int nwg, int nslots, int KVH, int G,
                                       int T, int causal) {
-  AtGq a;
+  AtOwn a;
   const int bid = blockIdx.x;
   const int first = 4 * (nwg - 1 - bid % nwg);   // later slots launch first
   const int bc = bid / nwg;
@@ -573,17 +317,18 @@ __device__ __forceinline__ AtGq at_gq(int nwg, int nslots, int KVH, int G,
   return a;
 }
 
-template <int D, bool VEC, bool DROP>
+template <int D, bool VEC, bool DROP, bool GROUPED>
 __global__ void __launch_bounds__(AT_THREADS)
-gqa_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
-               const uint16_t* __restrict__ k, long long ldk,
-               const uint16_t* __restrict__ v, long long ldv,
-               uint16_t* __restrict__ o, long long ldo,
-               float* __restrict__ lse, int T, int NH, int KVH, int nwg,
-               int nslots, int causal, float c2, AtDrop dr) {
+attn_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
+                const uint16_t* __restrict__ k, long long ldk,
+                const uint16_t* __restrict__ v, long long ldv,
+                uint16_t* __restrict__ o, long long ldo,
+                float* __restrict__ lse, int T, int NH, int KVH, int nwg,
+                int nslots, int causal, float c2, AtDrop dr) {
   __shared__ __attribute__((aligned(16))) uint16_t kimg[32 * D];
   __shared__ __attribute__((aligned(16))) uint16_t vtimg[D * AT_TRP];
-  const AtGq id = at_gq(nwg, nslots, KVH, NH / KVH, T, causal);
+  const AtOwn id = GROUPED ? at_gq(nwg, nslots, KVH, NH / KVH, T, causal)
+                          : at_plain(nwg, NH, T, causal);
   const long long row0 = (long long)id.b * T;
   q += row0 * ldq + id.h * D;
   o += row0 * ldo + id.h * D;
@@ -668,20 +413,21 @@ gqa_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
   }
 }
 
-template <int D, bool VEC, bool DROP>
+template <int D, bool VEC, bool DROP, bool GROUPED>
 __global__ void __launch_bounds__(AT_THREADS)
-gqa_dq_kernel(const uint16_t* __restrict__ q, long long ldq,
-              const uint16_t* __restrict__ k, long long ldk,
-              const uint16_t* __restrict__ v, long long ldv,
-              const uint16_t* __restrict__ dout, long long lddo,
-              const float* __restrict__ lse, const float* __restrict__ delta,
-              uint16_t* __restrict__ dq, long long lddq, int T, int NH,
-              int KVH, int nwg, int nslots, int causal, float c2, float scale,
-              AtDrop dr) {
+attn_dq_kernel(const uint16_t* __restrict__ q, long long ldq,
+               const uint16_t* __restrict__ k, long long ldk,
+               const uint16_t* __restrict__ v, long long ldv,
+               const uint16_t* __restrict__ dout, long long lddo,
+               const float* __restrict__ lse, const float* __restrict__ delta,
+               uint16_t* __restrict__ dq, long long lddq, int T, int NH,
+               int KVH, int nwg, int nslots, int causal, float c2, float scale,
+               AtDrop dr) {
   __shared__ __attribute__((aligned(16))) uint16_t kimg[32 * D];
   __shared__ __attribute__((aligned(16))) uint16_t vimg[32 * D];
   __shared__ __attribute__((aligned(16))) uint16_t ktimg[D * AT_TRP];
-  const AtGq id = at_gq(nwg, nslots, KVH, NH / KVH, T, causal);
+  const AtOwn id = GROUPED ? at_gq(nwg, nslots, KVH, NH / KVH, T, causal)
+                          : at_plain(nwg, NH, T, causal);
   const long long row0 = (long long)id.b * T;
   q += row0 * ldq + id.h * D;
   dout += row0 * lddo + id.h * D;
@@ -755,17 +501,17 @@ gqa_dq_kernel(const uint16_t* __restrict__ q, long long ldq,
 // within a head, into the same dK^T / dV^T accumulators: the group sum is
 // taken in float32 in that one order and rounded to bf16 once, at the store.
 // lse, delta and the 32 row seeds of a tile are those of its head.
-template <int D, bool VEC, bool DROP>
+template <int D, bool VEC, bool DROP, bool GROUPED>
 __global__ void __launch_bounds__(AT_THREADS)
-gqa_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
-               const uint16_t* __restrict__ k, long long ldk,
-               const uint16_t* __restrict__ v, long long ldv,
-               const uint16_t* __restrict__ dout, long long lddo,
-               const float* __restrict__ lse, const float* __restrict__ delta,
-               uint16_t* __restrict__ dk, long long lddk,
-               uint16_t* __restrict__ dv, long long lddv, int T, int NH,
-               int KVH, int ntiles, int causal, float c2, float scale,
-               AtDrop dr) {
+attn_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
+                const uint16_t* __restrict__ k, long long ldk,
+                const uint16_t* __restrict__ v, long long ldv,
+                const uint16_t* __restrict__ dout, long long lddo,
+                const float* __restrict__ lse, const float* __restrict__ delta,
+                uint16_t* __restrict__ dk, long long lddk,
+                uint16_t* __restrict__ dv, long long lddv, int T, int NH,
+                int KVH, int ntiles, int causal, float c2, float scale,
+                AtDrop dr) {
   __shared__ __attribute__((aligned(16))) uint16_t qimg[32 * D];
   __shared__ __attribute__((aligned(16))) uint16_t doimg[32 * D];
   __shared__ __attribute__((aligned(16))) uint16_t qtimg[D * AT_TRP];
@@ -773,7 +519,7 @@ gqa_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
   __shared__ float rowc[2][AT_SWEEP];   // lse * log2(e), delta of the tile
   __shared__ uint32_t rowsd[DROP ? AT_SWEEP : 1];   // mask row seeds of it
   const AtIds id = at_ids(ntiles, KVH, false);   // id.h: the K/V head c
-  const int G = NH / KVH, h0 = id.h * G;
+  const int G = GROUPED ? NH / KVH : 1, h0 = id.h * G;
   const long long row0 = (long long)id.b * T;
   q += row0 * ldq + h0 * D;
   dout += row0 * lddo + h0 * D;
@@ -883,9 +629,16 @@ inline bool at_shape_ok(int B, int T, int NH, int D) {
          tiles * B * NH < (1ll << 31);
 }
 inline float at_scale(int D) { return 1.f / sqrtf((float)D); }
+// G = NH / KVH query heads per K/V head; KVH = NH is plain multi-head
+inline bool gq_shape_ok(int B, int T, int NH, int KVH, int D) {
+  return at_shape_ok(B, T, NH, D) && KVH >= 1 && KVH <= NH && NH % KVH == 0;
+}
+// fwd, dq: workgroups of four slots per (batch, K/V head): at most
+// ceil(T / 128) G
+inline int gq_slots(int T, int G) { return (T + 31) / 32 * G; }
 
-// KERNEL<D, VEC TAIL> by the runtime D and vec; TAIL is empty or HVK_AT_DROP
-#define HVK_AT_DROP , DROP
+// KERNEL<D, VEC TAIL> by the runtime D and vec; TAIL is empty or HVK_AT_FLAGS
+#define HVK_AT_FLAGS , DROP, GROUPED
 #define HVK_AT_LAUNCH(K, grid, ...) \
   hipLaunchKernelGGL(K, grid, dim3(AT_THREADS), 0, s, __VA_ARGS__)
 #define HVK_AT_DISPATCH(KERNEL, TAIL, grid, ...)                       \
@@ -919,94 +672,18 @@ inline bool at_drop_ok(const uint32_t* seed_dev, float p, long long base_row,
   return true;
 }
 
-template <bool DROP>
-int at_fwd(const void* q, long long ldq, const void* k, long long ldk,
-           const void* v, long long ldv, void* o, long long ldo, float* lse,
-           int B, int T, int NH, int D, int causal, AtDrop dr,
-           hipStream_t s) {
-  if (!at_shape_ok(B, T, NH, D) || !lse) return -1;
-  const long long rows = (long long)B * T;
-  const int E = NH * D;
-  if (!at_view_ok(q, ldq, rows, E) || !at_view_ok(k, ldk, rows, E) ||
-      !at_view_ok(v, ldv, rows, E) || !at_view_ok(o, ldo, rows, E))
-    return -1;
-  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
-                   at_on16(o, ldo);
-  const int ntiles = (T + AT_OWN - 1) / AT_OWN;
-  const dim3 grid((unsigned)((long long)ntiles * B * NH));
-  HVK_AT_DISPATCH(attn_fwd_kernel, HVK_AT_DROP, grid, (const uint16_t*)q, ldq,
-                  (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
-                  (uint16_t*)o, ldo, lse, T, NH, ntiles, causal != 0,
-                  at_scale(D) * AT_LOG2E, dr);
-  return (int)launch_status(s);
-}
-
-template <bool DROP>
-int at_bwd_dkv(const void* q, long long ldq, const void* k, long long ldk,
-               const void* v, long long ldv, const void* dout, long long lddo,
-               const float* lse, const float* delta, void* dk, long long lddk,
-               void* dv, long long lddv, int B, int T, int NH, int D,
-               int causal, AtDrop dr, hipStream_t s) {
-  if (!at_shape_ok(B, T, NH, D) || !lse || !delta) return -1;
-  const long long rows = (long long)B * T;
-  const int E = NH * D;
-  if (!at_view_ok(q, ldq, rows, E) || !at_view_ok(k, ldk, rows, E) ||
-      !at_view_ok(v, ldv, rows, E) || !at_view_ok(dout, lddo, rows, E) ||
-      !at_view_ok(dk, lddk, rows, E) || !at_view_ok(dv, lddv, rows, E))
-    return -1;
-  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
-                   at_on16(dout, lddo) && at_on16(dk, lddk) &&
-                   at_on16(dv, lddv);
-  const int ntiles = (T + AT_OWN - 1) / AT_OWN;
-  const dim3 grid((unsigned)((long long)ntiles * B * NH));
-  HVK_AT_DISPATCH(attn_dkv_kernel, HVK_AT_DROP, grid, (const uint16_t*)q, ldq,
-                  (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
-                  (const uint16_t*)dout, lddo, lse, delta, (uint16_t*)dk, lddk,
-                  (uint16_t*)dv, lddv, T, NH, ntiles, causal != 0,
-                  at_scale(D) * AT_LOG2E, at_scale(D), dr);
-  return (int)launch_status(s);
-}
-
-template <bool DROP>
-int at_bwd_dq(const void* q, long long ldq, const void* k, long long ldk,
-              const void* v, long long ldv, const void* dout, long long lddo,
-              const float* lse, const float* delta, void* dq, long long lddq,
-              int B, int T, int NH, int D, int causal, AtDrop dr,
-              hipStream_t s) {
-  if (!at_shape_ok(B, T, NH, D) || !lse || !delta) return -1;
-  const long long rows = (long long)B * T;
-  const int E = NH * D;
-  if (!at_view_ok(q, ldq, rows, E) || !at_view_ok(k, ldk, rows, E) ||
-      !at_view_ok(v, ldv, rows, E) || !at_view_ok(dout, lddo, rows, E) ||
-      !at_view_ok(dq, lddq, rows, E))
-    return -1;
-  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
-                   at_on16(dout, lddo) && at_on16(dq, lddq);
-  const int ntiles = (T + AT_OWN - 1) / AT_OWN;
-  const dim3 grid((unsigned)((long long)ntiles * B * NH));
-  HVK_AT_DISPATCH(attn_dq_kernel, HVK_AT_DROP, grid, (const uint16_t*)q, ldq,
-                  (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
-                  (const uint16_t*)dout, lddo, lse, delta, (uint16_t*)dq, lddq,
-                  T, NH, ntiles, causal != 0, at_scale(D) * AT_LOG2E,
-                  at_scale(D), dr);
-  return (int)launch_status(s);
-}
-
-// grouped-query heads: the shape, and p == 0 with a null seed = no dropout
-inline bool gq_shape_ok(int B, int T, int NH, int KVH, int D) {
-  return at_shape_ok(B, T, NH, D) && KVH >= 1 && KVH <= NH && NH % KVH == 0;
-}
+// hvk_gqa_*: p == 0 with a null seed = no dropout
 inline bool gq_drop_ok(const uint32_t* seed_dev, float p, long long base_row,
                        AtDrop* dr, bool* drop) {
   *drop = !(p == 0.f && !seed_dev);
   *dr = AtDrop{};
   return !*drop || at_drop_ok(seed_dev, p, base_row, dr);
 }
-// workgroups of four slots per (batch, K/V head): at most ceil(T / 128) G
-inline int gq_slots(int T, int G) { return (T + 31) / 32 * G; }
 
-template <bool DROP>
-int gq_fwd(const void* q, long long ldq, const void* k, long long ldk,
+// The launchers.  k, v, dk and dv are checked at width KVH D, which at
+// KVH = NH is the width of the others.
+template <bool DROP, bool GROUPED>
+int at_fwd(const void* q, long long ldq, const void* k, long long ldk,
            const void* v, long long ldv, void* o, long long ldo, float* lse,
            int B, int T, int NH, int KVH, int D, int causal, AtDrop dr,
            hipStream_t s) {
@@ -1020,15 +697,15 @@ int gq_fwd(const void* q, long long ldq, const void* k, long long ldk,
                    at_on16(o, ldo);
   const int nslots = gq_slots(T, NH / KVH), nwg = (nslots + 3) / 4;
   const dim3 grid((unsigned)((long long)nwg * B * KVH));
-  HVK_AT_DISPATCH(gqa_fwd_kernel, HVK_AT_DROP, grid, (const uint16_t*)q, ldq,
+  HVK_AT_DISPATCH(attn_fwd_kernel, HVK_AT_FLAGS, grid, (const uint16_t*)q, ldq,
                   (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
                   (uint16_t*)o, ldo, lse, T, NH, KVH, nwg, nslots,
                   causal != 0, at_scale(D) * AT_LOG2E, dr);
   return (int)launch_status(s);
 }
 
-template <bool DROP>
-int gq_bwd_dkv(const void* q, long long ldq, const void* k, long long ldk,
+template <bool DROP, bool GROUPED>
+int at_bwd_dkv(const void* q, long long ldq, const void* k, long long ldk,
                const void* v, long long ldv, const void* dout, long long lddo,
                const float* lse, const float* delta, void* dk, long long lddk,
                void* dv, long long lddv, int B, int T, int NH, int KVH, int D,
@@ -1045,7 +722,7 @@ int gq_bwd_dkv(const void* q, long long ldq, const void* k, long long ldk,
                    at_on16(dv, lddv);
   const int ntiles = (T + AT_OWN - 1) / AT_OWN;
   const dim3 grid((unsigned)((long long)ntiles * B * KVH));
-  HVK_AT_DISPATCH(gqa_dkv_kernel, HVK_AT_DROP, grid, (const uint16_t*)q, ldq,
+  HVK_AT_DISPATCH(attn_dkv_kernel, HVK_AT_FLAGS, grid, (const uint16_t*)q, ldq,
                   (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
                   (const uint16_t*)dout, lddo, lse, delta, (uint16_t*)dk, lddk,
                   (uint16_t*)dv, lddv, T, NH, KVH, ntiles, causal != 0,
@@ -1053,8 +730,8 @@ int gq_bwd_dkv(const void* q, long long ldq, const void* k, long long ldk,
   return (int)launch_status(s);
 }
 
-template <bool DROP>
-int gq_bwd_dq(const void* q, long long ldq, const void* k, long long ldk,
+template <bool DROP, bool GROUPED>
+int at_bwd_dq(const void* q, long long ldq, const void* k, long long ldk,
               const void* v, long long ldv, const void* dout, long long lddo,
               const float* lse, const float* delta, void* dq, long long lddq,
               int B, int T, int NH, int KVH, int D, int causal, AtDrop dr,
@@ -1070,7 +747,7 @@ int gq_bwd_dq(const void* q, long long ldq, const void* k, long long ldk,
                    at_on16(dout, lddo) && at_on16(dq, lddq);
   const int nslots = gq_slots(T, NH / KVH), nwg = (nslots + 3) / 4;
   const dim3 grid((unsigned)((long long)nwg * B * KVH));
-  HVK_AT_DISPATCH(gqa_dq_kernel, HVK_AT_DROP, grid, (const uint16_t*)q, ldq,
+  HVK_AT_DISPATCH(attn_dq_kernel, HVK_AT_FLAGS, grid, (const uint16_t*)q, ldq,
                   (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
                   (const uint16_t*)dout, lddo, lse, delta, (uint16_t*)dq, lddq,
                   T, NH, KVH, nwg, nslots, causal != 0,
@@ -1091,8 +768,8 @@ HVK_API int hvk_attn_fwd(const void* q, long long ldq, const void* k,
                          long long ldk, const void* v, long long ldv, void* o,
                          long long ldo, float* lse, int B, int T, int NH,
                          int D, int causal, hipStream_t s) {
-  return at_fwd<false>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, T, NH, D,
-                       causal, AtDrop{}, s);
+  return at_fwd<false, false>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, T, NH,
+                              NH, D, causal, AtDrop{}, s);
 }
 
 // delta [B][NH][T] = rowsum over a head's columns of do * o
@@ -1121,8 +798,9 @@ HVK_API int hvk_attn_bwd_dkv(const void* q, long long ldq, const void* k,
                              const float* lse, const float* delta, void* dk,
                              long long lddk, void* dv, long long lddv, int B,
                              int T, int NH, int D, int causal, hipStream_t s) {
-  return at_bwd_dkv<false>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk,
-                           lddk, dv, lddv, B, T, NH, D, causal, AtDrop{}, s);
+  return at_bwd_dkv<false, false>(q, ldq, k, ldk, v, ldv, dout, lddo, lse,
+                                  delta, dk, lddk, dv, lddv, B, T, NH, NH, D,
+                                  causal, AtDrop{}, s);
 }
 
 // dq from the same operands
@@ -1132,8 +810,9 @@ HVK_API int hvk_attn_bwd_dq(const void* q, long long ldq, const void* k,
                             const float* delta, void* dq, long long lddq,
                             int B, int T, int NH, int D, int causal,
                             hipStream_t s) {
-  return at_bwd_dq<false>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq,
-                          lddq, B, T, NH, D, causal, AtDrop{}, s);
+  return at_bwd_dq<false, false>(q, ldq, k, ldk, v, ldv, dout, lddo, lse,
+                                 delta, dq, lddq, B, T, NH, NH, D, causal,
+                                 AtDrop{}, s);
 }
 
 // The three kernels with dropout on P at probability p in [0, 1): the mask of
@@ -1149,8 +828,8 @@ HVK_API int hvk_adrop_fwd(const void* q, long long ldq, const void* k,
                           long long base_row, hipStream_t s) {
   AtDrop dr;
   if (!at_drop_ok(seed_dev, p, base_row, &dr)) return -1;
-  return at_fwd<true>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, T, NH, D,
-                      causal, dr, s);
+  return at_fwd<true, false>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, T, NH,
+                             NH, D, causal, dr, s);
 }
 
 HVK_API int hvk_adrop_bwd_dkv(const void* q, long long ldq, const void* k,
@@ -1163,8 +842,9 @@ HVK_API int hvk_adrop_bwd_dkv(const void* q, long long ldq, const void* k,
                               long long base_row, hipStream_t s) {
   AtDrop dr;
   if (!at_drop_ok(seed_dev, p, base_row, &dr)) return -1;
-  return at_bwd_dkv<true>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk,
-                          lddk, dv, lddv, B, T, NH, D, causal, dr, s);
+  return at_bwd_dkv<true, false>(q, ldq, k, ldk, v, ldv, dout, lddo, lse,
+                                 delta, dk, lddk, dv, lddv, B, T, NH, NH, D,
+                                 causal, dr, s);
 }
 
 HVK_API int hvk_adrop_bwd_dq(const void* q, long long ldq, const void* k,
@@ -1176,8 +856,9 @@ HVK_API int hvk_adrop_bwd_dq(const void* q, long long ldq, const void* k,
                              long long base_row, hipStream_t s) {
   AtDrop dr;
   if (!at_drop_ok(seed_dev, p, base_row, &dr)) return -1;
-  return at_bwd_dq<true>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq,
-                         lddq, B, T, NH, D, causal, dr, s);
+  return at_bwd_dq<true, false>(q, ldq, k, ldk, v, ldv, dout, lddo, lse,
+                                delta, dq, lddq, B, T, NH, NH, D, causal, dr,
+                                s);
 }
 
 // Grouped-query heads: k, v, dk and dv are [B][T][KVH*D], NH % KVH == 0, and
@@ -1193,10 +874,10 @@ HVK_API int hvk_gqa_fwd(const void* q, long long ldq, const void* k,
   AtDrop dr;
   bool drop;
   if (!gq_drop_ok(seed_dev, p, base_row, &dr, &drop)) return -1;
-  return drop ? gq_fwd<true>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, T, NH,
-                             KVH, D, causal, dr, s)
-              : gq_fwd<false>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, T, NH,
-                              KVH, D, causal, dr, s);
+  return drop ? at_fwd<true, true>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, T,
+                                   NH, KVH, D, causal, dr, s)
+              : at_fwd<false, true>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, T,
+                                    NH, KVH, D, causal, dr, s);
 }
 
 HVK_API int hvk_gqa_bwd_dkv(const void* q, long long ldq, const void* k,
@@ -1210,12 +891,12 @@ HVK_API int hvk_gqa_bwd_dkv(const void* q, long long ldq, const void* k,
   AtDrop dr;
   bool drop;
   if (!gq_drop_ok(seed_dev, p, base_row, &dr, &drop)) return -1;
-  return drop ? gq_bwd_dkv<true>(q, ldq, k, ldk, v, ldv, dout, lddo, lse,
-                                 delta, dk, lddk, dv, lddv, B, T, NH, KVH, D,
-                                 causal, dr, s)
-              : gq_bwd_dkv<false>(q, ldq, k, ldk, v, ldv, dout, lddo, lse,
-                                  delta, dk, lddk, dv, lddv, B, T, NH, KVH, D,
-                                  causal, dr, s);
+  return drop ? at_bwd_dkv<true, true>(q, ldq, k, ldk, v, ldv, dout, lddo,
+                                       lse, delta, dk, lddk, dv, lddv, B, T,
+                                       NH, KVH, D, causal, dr, s)
+              : at_bwd_dkv<false, true>(q, ldq, k, ldk, v, ldv, dout, lddo,
+                                        lse, delta, dk, lddk, dv, lddv, B, T,
+                                        NH, KVH, D, causal, dr, s);
 }
 
 HVK_API int hvk_gqa_bwd_dq(const void* q, long long ldq, const void* k,
@@ -1228,10 +909,10 @@ HVK_API int hvk_gqa_bwd_dq(const void* q, long long ldq, const void* k,
   AtDrop dr;
   bool drop;
   if (!gq_drop_ok(seed_dev, p, base_row, &dr, &drop)) return -1;
-  return drop ? gq_bwd_dq<true>(q, ldq, k, ldk, v, ldv, dout, lddo, lse,
-                                delta, dq, lddq, B, T, NH, KVH, D, causal, dr,
-                                s)
-              : gq_bwd_dq<false>(q, ldq, k, ldk, v, ldv, dout, lddo, lse,
-                                 delta, dq, lddq, B, T, NH, KVH, D, causal,
-                                 dr, s);
+  return drop ? at_bwd_dq<true, true>(q, ldq, k, ldk, v, ldv, dout, lddo,
+                                      lse, delta, dq, lddq, B, T, NH, KVH, D,
+                                      causal, dr, s)
+              : at_bwd_dq<false, true>(q, ldq, k, ldk, v, ldv, dout, lddo,
+                                       lse, delta, dq, lddq, B, T, NH, KVH, D,
+                                       causal, dr, s);
 }

@@ -12,7 +12,10 @@ bound.  The summed dk / dv of the full run is then held to the sum of those
 pieces: both are bf16 roundings of float32 sums over the same products, one
 chain of G T terms against G chains of T, so they differ by the G + 1 half
 ulps and 2 gamma(G T) sum |term|; sum |term| is bounded from the p = 0 oracle
-(P~ <= P / (1 - p); |dS~| <= P (|dP| + sum_j P |dP|) / ((1 - p) sqrt(D)))."""
+(P~ <= P / (1 - p); |dS~| <= P (|dP| + sum_j P |dP|) / ((1 - p) sqrt(D))).
+
+One group (KVH = NH) through the same entries gives the bits of hvk_attn_* and
+hvk_adrop_*: the kernels are one code, and ops never takes that route."""
 import math
 import os
 
@@ -205,6 +208,54 @@ def test_layer_within_the_bound_and_graph_replays():
                        zip(list(out.values()) + kept, want))
     finally:
         ops.set_deterministic(False)
+
+
+def gqa_direct(case, NH, causal, p=0.0, seed_dev=None):
+    """hvk_gqa_* called at KVH = NH, where ops takes hvk_attn_* / hvk_adrop_*"""
+    q, k, v, do = case
+    B, T, E = q.shape
+    o, dq, dk, dv = (torch.empty(B, T, E, dtype=BF, device="cuda")
+                     for _ in range(4))
+    lse, delta = (torch.empty(B, NH, T, device="cuda") for _ in "01")
+    lib, s = ops._lib.lib(), torch.cuda.current_stream().cuda_stream
+
+    def at(*ts):
+        return [x for t in ts for x in (t.data_ptr(), t.stride(1))]
+    tail = [B, T, NH, NH, E // NH, int(causal),
+            None if seed_dev is None else seed_dev.data_ptr(), p, 0, s]
+    bwd = at(q, k, v, do) + [lse.data_ptr(), delta.data_ptr()]
+    rcs = (lib.hvk_gqa_fwd(*at(q, k, v, o), lse.data_ptr(), *tail),
+           lib.hvk_attn_bwd_delta(*at(do, o), delta.data_ptr(), B, T, NH,
+                                  E // NH, s),
+           lib.hvk_gqa_bwd_dkv(*bwd, *at(dk, dv), *tail),
+           lib.hvk_gqa_bwd_dq(*bwd, *at(dq), *tail))
+    assert rcs == (0, 0, 0, 0)
+    return {"o": o, "lse": lse, "dq": dq, "dk": dk, "dv": dv}
+
+
+def same_as_the_plain_entries(gv, NH, causal):
+    for p, sd in ((0.0, None), (0.5, seed_tensor(4321))):
+        kw = dict(dropout=p, seed_dev=sd) if p else {}
+        plain = run_gqa(gv, NH, NH, causal, **kw)
+        got = gqa_direct(gv, NH, causal, p, sd)
+        for n in NAMES:
+            assert same_bits(got[n], plain[n]), (n, p)
+
+
+@pytest.mark.parametrize("D", (32, 128))
+@pytest.mark.parametrize("causal", (False, True))
+def test_one_group_gives_the_bits_of_the_plain_entries(D, causal):
+    """G = 1 is the plain geometry: hvk_gqa_* at KVH = NH against hvk_attn_*
+    (p = 0, null seed) and hvk_adrop_* (p = 0.5).  T = TQ + TK + 1: the second
+    owned tile has one full wave, one wave with a single row, two idle"""
+    same_as_the_plain_entries(
+        views(gqa_case(2, TQ + TK + 1, 3, 3, D, seed=7)), 3, causal)
+
+
+def test_one_group_gives_the_bits_of_the_plain_entries_element_path():
+    gv = views(gqa_case(2, TQ + TK + 1, 3, 3, 32, seed=7), pad=1)
+    assert gv[0].stride(1) % 8 == 1
+    same_as_the_plain_entries(gv, 3, True)
 
 
 def test_entry_points_reject_before_any_launch():
