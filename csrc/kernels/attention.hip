@@ -170,14 +170,6 @@ __device__ __forceinline__ int at_accrow(int i, int hh) {
   return (i & 3) + 8 * (i >> 2) + 4 * hh;
 }
 
-// the counter hash of elementwise.hip (dropout, stochastic pooling)
-__device__ __forceinline__ uint32_t at_hash32(uint32_t x, uint32_t seed) {
-  x ^= seed * 0x9E3779B9u;
-  x ^= x >> 16; x *= 0x7feb352du;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
 // dropout on P: the device seed, keep iff hash >= thresh, inv = 1 / (1 - p),
 // row0 = the rank's first sample in the global minibatch (mod 2^32)
 struct AtDrop {
@@ -190,8 +182,8 @@ struct AtDrop {
 __device__ __forceinline__ uint32_t at_rowseed(const AtDrop& dr, int b, int h,
                                                int NH, int T, int i,
                                                uint32_t seed) {
-  return at_hash32(((dr.row0 + (uint32_t)b) * (uint32_t)NH + (uint32_t)h) *
-                       (uint32_t)T + (uint32_t)i, seed);
+  return hash32(((dr.row0 + (uint32_t)b) * (uint32_t)NH + (uint32_t)h) *
+                    (uint32_t)T + (uint32_t)i, seed);
 }
 
 // the 128-row tile and the (batch, head) of a workgroup
@@ -395,7 +387,7 @@ attn_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
     if constexpr (DROP) {   // l took the undropped exponentials
 #pragma unroll
       for (int i = 0; i < 16; ++i)
-        if (at_hash32((uint32_t)(k0 + at_accrow(i, hh)), rseed) < dr.thresh)
+        if (hash32((uint32_t)(k0 + at_accrow(i, hh)), rseed) < dr.thresh)
           p[i] = 0.f;
     }
     const bf16x8 pb[2] = {at_pack8(p), at_pack8(p + 8)};
@@ -481,7 +473,7 @@ attn_dq_kernel(const uint16_t* __restrict__ q, long long ldq,
       }
       float dp = pacc[i];
       if constexpr (DROP)
-        dp = at_hash32((uint32_t)(k0 + at_accrow(i, hh)), rseed) >= dr.thresh
+        dp = hash32((uint32_t)(k0 + at_accrow(i, hh)), rseed) >= dr.thresh
                  ? dp * dr.inv : 0.f;
       ds[i] = pv * (dp - dl) * scale;
     }
@@ -586,7 +578,7 @@ attn_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
       }
       float dp = pacc[i];
       if constexpr (DROP) {
-        const bool keep = at_hash32((uint32_t)kj, rowsd[qr]) >= dr.thresh;
+        const bool keep = hash32((uint32_t)kj, rowsd[qr]) >= dr.thresh;
         p[i] = keep ? pv : 0.f;
         dp = keep ? dp * dr.inv : 0.f;
       } else {
@@ -616,9 +608,6 @@ attn_dkv_kernel(const uint16_t* __restrict__ q, long long ldq,
 inline bool at_view_ok(const void* p, long long ld, long long rows, int E) {
   return p != nullptr && (((uintptr_t)p) & 1) == 0 && ld >= E &&
          rows * ld < (1ll << 31);
-}
-inline bool at_on16(const void* p, long long ld) {
-  return (((uintptr_t)p) & 15) == 0 && ld % 8 == 0;
 }
 inline bool at_shape_ok(int B, int T, int NH, int D) {
   if (B < 1 || T < 1 || NH < 1 || (D != 32 && D != 64 && D != 128))
@@ -693,8 +682,8 @@ int at_fwd(const void* q, long long ldq, const void* k, long long ldk,
   if (!at_view_ok(q, ldq, rows, E) || !at_view_ok(k, ldk, rows, EK) ||
       !at_view_ok(v, ldv, rows, EK) || !at_view_ok(o, ldo, rows, E))
     return -1;
-  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
-                   at_on16(o, ldo);
+  const bool vec =
+      on16(q, ldq) && on16(k, ldk) && on16(v, ldv) && on16(o, ldo);
   const int nslots = gq_slots(T, NH / KVH), nwg = (nslots + 3) / 4;
   const dim3 grid((unsigned)((long long)nwg * B * KVH));
   HVK_AT_DISPATCH(attn_fwd_kernel, HVK_AT_FLAGS, grid, (const uint16_t*)q, ldq,
@@ -717,9 +706,8 @@ int at_bwd_dkv(const void* q, long long ldq, const void* k, long long ldk,
       !at_view_ok(v, ldv, rows, EK) || !at_view_ok(dout, lddo, rows, E) ||
       !at_view_ok(dk, lddk, rows, EK) || !at_view_ok(dv, lddv, rows, EK))
     return -1;
-  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
-                   at_on16(dout, lddo) && at_on16(dk, lddk) &&
-                   at_on16(dv, lddv);
+  const bool vec = on16(q, ldq) && on16(k, ldk) && on16(v, ldv) &&
+                   on16(dout, lddo) && on16(dk, lddk) && on16(dv, lddv);
   const int ntiles = (T + AT_OWN - 1) / AT_OWN;
   const dim3 grid((unsigned)((long long)ntiles * B * KVH));
   HVK_AT_DISPATCH(attn_dkv_kernel, HVK_AT_FLAGS, grid, (const uint16_t*)q, ldq,
@@ -743,8 +731,8 @@ int at_bwd_dq(const void* q, long long ldq, const void* k, long long ldk,
       !at_view_ok(v, ldv, rows, EK) || !at_view_ok(dout, lddo, rows, E) ||
       !at_view_ok(dq, lddq, rows, E))
     return -1;
-  const bool vec = at_on16(q, ldq) && at_on16(k, ldk) && at_on16(v, ldv) &&
-                   at_on16(dout, lddo) && at_on16(dq, lddq);
+  const bool vec = on16(q, ldq) && on16(k, ldk) && on16(v, ldv) &&
+                   on16(dout, lddo) && on16(dq, lddq);
   const int nslots = gq_slots(T, NH / KVH), nwg = (nslots + 3) / 4;
   const dim3 grid((unsigned)((long long)nwg * B * KVH));
   HVK_AT_DISPATCH(attn_dq_kernel, HVK_AT_FLAGS, grid, (const uint16_t*)q, ldq,
@@ -781,7 +769,7 @@ HVK_API int hvk_attn_bwd_delta(const void* dout, long long lddo,
   const int E = NH * D;
   if (!at_view_ok(dout, lddo, rows, E) || !at_view_ok(o, ldo, rows, E))
     return -1;
-  const bool vec = at_on16(dout, lddo) && at_on16(o, ldo);
+  const bool vec = on16(dout, lddo) && on16(o, ldo);
   const long long nrows = rows * NH;
   const long long threads = nrows * (D / 8);
   const dim3 grid((unsigned)((threads + AT_THREADS - 1) / AT_THREADS));

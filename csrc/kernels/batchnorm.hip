@@ -69,41 +69,6 @@ inline BnGeom bn_geom(long long P, int C, bool vec) {
   return g;
 }
 
-// NV bf16 values at p -> float
-template <bool VEC>
-__device__ __forceinline__ void bn_load(const uint16_t* p, float* v) {
-  if constexpr (VEC) {
-    const uint4 u = *(const uint4*)p;
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      v[2 * q] = __uint_as_float(w[q] << 16);
-      v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u);
-    }
-  } else {
-    v[0] = bf2f(*p);
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void bn_store(uint16_t* p, const float* v) {
-  if constexpr (VEC) {
-    *(uint4*)p = pack_bf16x8(v);
-  } else {
-    *p = f2bf(v[0]);
-  }
-}
-// NV floats of a per-channel table
-template <bool VEC>
-__device__ __forceinline__ void bn_loadf(const float* p, float* v) {
-  if constexpr (VEC) {
-    const float4 a = ((const float4*)p)[0], b = ((const float4*)p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  } else {
-    v[0] = *p;
-  }
-}
-
 constexpr int BN_SHIFT_ROWS = 8;
 // The shift of NV channels at xc: their mean over the first rows, added in
 // row order (every caller gets the same bits)
@@ -116,7 +81,7 @@ __device__ __forceinline__ void bn_shift(const uint16_t* xc, long long ldx,
   for (int k = 0; k < NV; ++k) K[k] = 0.f;
   for (int r = 0; r < n; ++r) {
     float v[NV];
-    bn_load<VEC>(xc + r * ldx, v);
+    ld_bf16<VEC>(xc + r * ldx, v);
 #pragma unroll
     for (int k = 0; k < NV; ++k) K[k] += v[k];
   }
@@ -196,7 +161,7 @@ bn_stats_partial_kernel(const uint16_t* __restrict__ x, long long ldx,
 #pragma unroll 4
     for (long long r = (long long)blockIdx.y * RY + l.ty; r < P; r += step) {
       float v[NV];
-      bn_load<VEC>(xc + r * ldx, v);
+      ld_bf16<VEC>(xc + r * ldx, v);
 #pragma unroll
       for (int k = 0; k < NV; ++k) {
         const float d = v[k] - K[k];
@@ -266,17 +231,17 @@ bn_apply_kernel(const uint16_t* __restrict__ x, long long ldx,
   if (!l.on) return;
   const long long c0 = (long long)l.cg * NV;
   float sc[NV], sh[NV];
-  bn_loadf<VEC>(table + c0, sc);
-  bn_loadf<VEC>(table + C + c0, sh);
+  ld_f32<VEC>(table + c0, sc);
+  ld_f32<VEC>(table + C + c0, sh);
   const long long step = (long long)gridDim.y * RY;
 #pragma unroll 4
   for (long long r = (long long)blockIdx.y * RY + l.ty; r < P; r += step) {
     float v[NV];
-    bn_load<VEC>(x + r * ldx + c0, v);
+    ld_bf16<VEC>(x + r * ldx + c0, v);
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] = __builtin_fmaf(v[k], sc[k], sh[k]);
     act_fwd_n<NV>(v, ACT);
-    bn_store<VEC>(y + r * ldy + c0, v);
+    st_bf16<VEC>(y + r * ldy + c0, v);
   }
 }
 
@@ -300,17 +265,17 @@ bn_bwd_partial_kernel(const uint16_t* __restrict__ x, long long ldx,
   if (l.on) {
     const long long c0 = (long long)l.cg * NV;
     float mu[NV], is[NV];
-    bn_loadf<VEC>(mean + c0, mu);
-    bn_loadf<VEC>(invstd + c0, is);
+    ld_f32<VEC>(mean + c0, mu);
+    ld_f32<VEC>(invstd + c0, is);
     const long long step = (long long)gridDim.y * RY;
 #pragma unroll 2
     for (long long r = (long long)blockIdx.y * RY + l.ty; r < P; r += step) {
       float v[NV], g[NV];
-      bn_load<VEC>(x + r * ldx + c0, v);
-      bn_load<VEC>(err + r * lde + c0, g);
+      ld_bf16<VEC>(x + r * ldx + c0, v);
+      ld_bf16<VEC>(err + r * lde + c0, g);
       if (act) {
         float yv[NV];
-        bn_load<VEC>(y + r * ldy + c0, yv);
+        ld_bf16<VEC>(y + r * ldy + c0, yv);
         act_bwd_mul_n<NV>(g, yv, act);
       }
 #pragma unroll
@@ -359,19 +324,19 @@ bn_bwd_apply_kernel(const uint16_t* __restrict__ x, long long ldx,
   if (!l.on) return;
   const long long c0 = (long long)l.cg * NV;
   float mu[NV], A[NV], B[NV], D[NV];
-  bn_loadf<VEC>(mean + c0, mu);
-  bn_loadf<VEC>(coef + c0, A);
-  bn_loadf<VEC>(coef + C + c0, B);
-  bn_loadf<VEC>(coef + 2 * (long long)C + c0, D);
+  ld_f32<VEC>(mean + c0, mu);
+  ld_f32<VEC>(coef + c0, A);
+  ld_f32<VEC>(coef + C + c0, B);
+  ld_f32<VEC>(coef + 2 * (long long)C + c0, D);
   const long long step = (long long)gridDim.y * RY;
 #pragma unroll 2
   for (long long r = (long long)blockIdx.y * RY + l.ty; r < P; r += step) {
     float v[NV], g[NV];
-    bn_load<VEC>(x + r * ldx + c0, v);
-    bn_load<VEC>(err + r * lde + c0, g);
+    ld_bf16<VEC>(x + r * ldx + c0, v);
+    ld_bf16<VEC>(err + r * lde + c0, g);
     if (act) {
       float yv[NV];
-      bn_load<VEC>(y + r * ldy + c0, yv);
+      ld_bf16<VEC>(y + r * ldy + c0, yv);
       act_bwd_mul_n<NV>(g, yv, act);
     }
 #pragma unroll
@@ -380,18 +345,15 @@ bn_bwd_apply_kernel(const uint16_t* __restrict__ x, long long ldx,
                             __builtin_fmaf(B[k], v[k] - mu[k], D[k]));
     if (aux_act) {
       float av[NV];
-      bn_load<VEC>(aux + r * lda + c0, av);
+      ld_bf16<VEC>(aux + r * lda + c0, av);
       act_bwd_mul_n<NV>(v, av, aux_act);
     }
-    bn_store<VEC>(dx + r * lddx + c0, v);
+    st_bf16<VEC>(dx + r * lddx + c0, v);
   }
 }
 
 inline bool bn_shape_ok(long long P, int C) {
   return P >= 1 && C >= 1 && P <= ((1ll << 31) - 1) / C;
-}
-inline bool on16(const void* p, long long ld) {
-  return p == nullptr || ((((uintptr_t)p) & 15) == 0 && ld % 8 == 0);
 }
 inline bool pitch_ok(const void* p, long long ld, int C) {
   return p == nullptr || ld >= C;
@@ -427,7 +389,7 @@ HVK_API int hvk_bn_partials(long long P, int C, int vec) {
 // 1 when a [P][C] tensor at x with row pitch ldx (elements) takes the
 // vector path
 HVK_API int hvk_bn_vec(const void* x, long long ldx, int C) {
-  return C % 8 == 0 && on16(x, ldx) ? 1 : 0;
+  return C % 8 == 0 && on16_or_null(x, ldx) ? 1 : 0;
 }
 
 // Training statistics of x[P][C] (bf16, row pitch ldx elements, P >= 2):
@@ -510,8 +472,9 @@ HVK_API int hvk_bn_bwd(const void* x, long long ldx, const void* err,
     return -1;
   if (!act) y = nullptr;
   if (!aux_act) aux = nullptr;
-  if (vec && !(C % 8 == 0 && on16(x, ldx) && on16(err, lde) && on16(y, ldy) &&
-               on16(aux, lda) && on16(dx, lddx)))
+  if (vec && !(C % 8 == 0 && on16(x, ldx) && on16(err, lde) &&
+               on16_or_null(y, ldy) && on16_or_null(aux, lda) &&
+               on16_or_null(dx, lddx)))
     return -1;
   const BnGeom g = bn_geom(P, C, vec != 0);
   const dim3 grid(g.NTX, g.G), grida(g.NTX, g.GA);

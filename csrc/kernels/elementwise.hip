@@ -617,14 +617,7 @@ __global__ void relu_bwd_bf16x8_kernel(const uint16_t* dy, const uint16_t* y,
 
 // --------------------------------------------------------------- dropout
 // Counter-based mask (no state; the backward pass regenerates it):
-//   keep(i) = hash(seed, i) >= p * 2^32 ; y = keep ? x / (1-p) : 0
-__device__ __forceinline__ uint32_t hash32(uint32_t x, uint32_t seed) {
-  x ^= seed * 0x9E3779B9u;
-  x ^= x >> 16; x *= 0x7feb352du;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
+//   keep(i) = hash32(i, seed) >= p * 2^32 ; y = keep ? x / (1-p) : 0
 // seed_dev (optional): the seed is read from device memory instead, so a
 // captured HIP graph draws a fresh mask every replay (hvk_seed_advance).
 // element i's mask is hash32(base + i, seed): a rank passes the global index

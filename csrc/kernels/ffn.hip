@@ -122,15 +122,6 @@ __device__ __forceinline__ float ffn_dact(float dh, float u) {
   }
 }
 
-__device__ __forceinline__ void ffn_unpack8(const uint4 p, float* v) {
-  const uint32_t w[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    v[2 * q] = __uint_as_float(w[q] << 16);
-    v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u);
-  }
-}
-
 // ---------------------------------------------------------------- forward
 template <bool VEC, int ACT>
 __global__ void __launch_bounds__(FFN_THREADS)
@@ -144,7 +135,7 @@ ffn_fwd_kernel(const uint16_t* u, long long ldu, uint16_t* h, long long ldh,
       const long long c0 = cg * NV;
       if constexpr (VEC) {
         float v[8];
-        ffn_unpack8(*(const uint4*)(u + row * ldu + c0), v);
+        unpack_bf16x8(*(const uint4*)(u + row * ldu + c0), v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = ffn_act<ACT>(v[j]);
         *(uint4*)(h + row * ldh + c0) = pack_bf16x8(v);
@@ -180,13 +171,13 @@ ffn_bwd_row_kernel(const uint16_t* dh, long long lddh,
          row += step) {
       if constexpr (VEC) {
         float g[8], v[8];
-        ffn_unpack8(*(const uint4*)(dh + row * lddh + c0), g);
-        ffn_unpack8(*(const uint4*)(u + row * ldu + c0), v);
+        unpack_bf16x8(*(const uint4*)(dh + row * lddh + c0), g);
+        unpack_bf16x8(*(const uint4*)(u + row * ldu + c0), v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) g[j] = ffn_dact<ACT>(g[j], v[j]);
         const uint4 p = pack_bf16x8(g);
         *(uint4*)(du + row * lddu + c0) = p;
-        ffn_unpack8(p, g);
+        unpack_bf16x8(p, g);
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] += g[j];
       } else {
@@ -242,10 +233,10 @@ ffn_bwd_tile_kernel(const uint16_t* dh, long long lddh,
       const uint4* pu = (const uint4*)(u + row * ldu + c0 + rr);
       const uint4 g0 = pg[0], g1 = pg[1], u0 = pu[0], u1 = pu[1];
       float g[16], v[16];
-      ffn_unpack8(g0, g);
-      ffn_unpack8(g1, g + 8);
-      ffn_unpack8(u0, v);
-      ffn_unpack8(u1, v + 8);
+      unpack_bf16x8(g0, g);
+      unpack_bf16x8(g1, g + 8);
+      unpack_bf16x8(u0, v);
+      unpack_bf16x8(u1, v + 8);
 #pragma unroll
       for (int j = 0; j < 16; ++j) g[j] = ffn_dact<ACT>(g[j], v[j]);
       const uint4 a = pack_bf16x8(g), b = pack_bf16x8(g + 8);
@@ -304,9 +295,6 @@ inline bool ffn_shape_ok(long long P, int F) {
 inline bool ffn_pitch_ok(long long P, int F, long long ld) {
   return ld >= F && (P - 1) * ld + F < (1ll << 31);
 }
-inline bool ffn_on16(const void* p, long long ld) {
-  return p == nullptr || ((((uintptr_t)p) & 15) == 0 && ld % 8 == 0);
-}
 inline int ffn_tile_rt(long long P) { return P % 256 == 0 ? 4 : 1; }
 inline int ffn_row_slabs(long long P) {
   const long long per = (long long)FFN_ROW_SUBS * FFN_ROW_MIN;
@@ -334,7 +322,7 @@ HVK_API int hvk_ffn_act_fwd(const void* u, long long ldu, void* h,
   if (!u || !h || !ffn_shape_ok(P, F) || !ffn_pitch_ok(P, F, ldu) ||
       !ffn_pitch_ok(P, F, ldh) || act < 0 || act > 2)
     return -1;
-  const bool vec = F % 8 == 0 && ffn_on16(u, ldu) && ffn_on16(h, ldh);
+  const bool vec = F % 8 == 0 && on16(u, ldu) && on16(h, ldh);
   long long rows = P, cols = F;
   if (ldu == F && ldh == F) {   // one long row
     cols = P * F;
@@ -374,11 +362,11 @@ HVK_API int hvk_ffn_act_bwd(const void* dh, long long lddh, const void* u,
       !ffn_pitch_ok(P, F, lddh) || !ffn_pitch_ok(P, F, ldu) ||
       !ffn_pitch_ok(P, F, lddu) || act < 0 || act > 2)
     return -1;
-  const bool vec = F % 8 == 0 && ffn_on16(dh, lddh) && ffn_on16(u, ldu) &&
-                   ffn_on16(du, lddu) && ffn_on16(ws, 8);
+  const bool vec = F % 8 == 0 && on16(dh, lddh) && on16(u, ldu) &&
+                   on16(du, lddu) && on16(ws, 8);
   int G;
   if (dut) {
-    if (P % 64 || F % 64 || !vec || !ffn_on16(dut, lddut) || lddut < P ||
+    if (P % 64 || F % 64 || !vec || !on16(dut, lddut) || lddut < P ||
         (F - 1) * lddut + P >= (1ll << 31))
       return -1;
     const int rt = ffn_tile_rt(P);

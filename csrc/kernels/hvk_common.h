@@ -57,6 +57,84 @@ __device__ __forceinline__ uint4 pack_bf16x8(const float* v) {
   return make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]),
                     pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
 }
+// bf16 -> f32 is exact: the 16 bits become the high half of the f32
+__device__ __forceinline__ void unpack_bf16x2(uint32_t w, float* v) {
+  v[0] = __uint_as_float(w << 16);
+  v[1] = __uint_as_float(w & 0xffff0000u);
+}
+__device__ __forceinline__ void unpack_bf16x8(const uint4 p, float* v) {
+  unpack_bf16x2(p.x, v);
+  unpack_bf16x2(p.y, v + 2);
+  unpack_bf16x2(p.z, v + 4);
+  unpack_bf16x2(p.w, v + 6);
+}
+
+// The row accessors of the element-wise passes: 8 consecutive values in
+// 16-byte accesses when VEC (the host checked on16 and a width % 8 == 0),
+// else one value.
+template <bool VEC>
+__device__ __forceinline__ void ld_bf16(const uint16_t* p, float* v) {
+  if constexpr (VEC) {
+    unpack_bf16x8(*(const uint4*)p, v);
+  } else {
+    v[0] = bf2f(*p);
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void st_bf16(uint16_t* p, const float* v) {
+  if constexpr (VEC) {
+    *(uint4*)p = pack_bf16x8(v);
+  } else {
+    *p = f2bf(v[0]);
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void ld_f32(const float* p, float* v) {
+  if constexpr (VEC) {
+    const float4 a = ((const float4*)p)[0], b = ((const float4*)p)[1];
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  } else {
+    v[0] = *p;
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void st_f32(float* p, const float* v) {
+  if constexpr (VEC) {
+    ((float4*)p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+    ((float4*)p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+  } else {
+    *p = v[0];
+  }
+}
+
+// Host side of VEC: base on the 16-byte grid and a pitch (in bf16 elements,
+// or 8 for a table) that keeps every row there.  on16_or_null also passes an
+// absent (nullptr) operand.
+inline bool on16(const void* p, long long ld) {
+  return (((uintptr_t)p) & 15) == 0 && ld % 8 == 0;
+}
+inline bool on16_or_null(const void* p, long long ld) {
+  return p == nullptr || on16(p, ld);
+}
+
+// The counter hash behind every mask and sample (dropout, attention dropout,
+// RBM sampling): element i of a stream draws hash32(i, seed), so a rank that
+// passes its global index draws the bits a single process would.  ops._hash32
+// in veles_amd/ops/__init__.py is its Python mirror: the two change together.
+__device__ __forceinline__ uint32_t hash32(uint32_t x, uint32_t seed) {
+  x ^= seed * 0x9E3779B9u;
+  x ^= x >> 16; x *= 0x7feb352du;
+  x ^= x >> 15; x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+// plain logistic function; +-inf arguments of the division give exactly 0 / 1
+__device__ __forceinline__ float sigm(float x) {
+  return 1.f / (1.f + __expf(-x));
+}
+
 // Strict ReLU on a packed bf16 pair as 16-bit integers: a bf16 is > 0
 // exactly when its bit pattern is a positive int16, so max(x, 0) and the
 // derivative mask (x > 0 ? 0xffff : 0) are one / three packed-i16 ops per
@@ -122,7 +200,7 @@ __device__ __forceinline__ float act_fwd(float x, int act) {
     case ACT_TANH: return 1.7159f * tanhf(0.6666f * x);
     case ACT_RELU: return x > 15.f ? x : log1pf(__expf(x));
     case ACT_STRICT_RELU: return x > 0.f ? x : 0.f;
-    case ACT_SIGMOID: return 1.f / (1.f + __expf(-x));
+    case ACT_SIGMOID: return sigm(x);
     default: return x;
   }
 }
@@ -147,7 +225,7 @@ __device__ __forceinline__ void act_fwd_n(float* v, int act) {
       return;
     case ACT_SIGMOID:
 #pragma unroll
-      for (int q = 0; q < NV; ++q) v[q] = 1.f / (1.f + __expf(-v[q]));
+      for (int q = 0; q < NV; ++q) v[q] = sigm(v[q]);
       return;
     default:
       return;

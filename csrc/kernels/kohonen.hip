@@ -41,13 +41,10 @@ __device__ __forceinline__ void ld4(const float* p, float* v) {
   const float4 f = *(const float4*)p;
   v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
 }
-// bf16 -> f32 is exact: the 16 bits become the high half of the f32
 __device__ __forceinline__ void ld4(const uint16_t* p, float* v) {
   const uint2 u = *(const uint2*)p;
-  v[0] = __uint_as_float(u.x << 16);
-  v[1] = __uint_as_float(u.x & 0xffff0000u);
-  v[2] = __uint_as_float(u.y << 16);
-  v[3] = __uint_as_float(u.y & 0xffff0000u);
+  unpack_bf16x2(u.x, v);
+  unpack_bf16x2(u.y, v + 2);
 }
 
 // NI 16-B LDS chunks per thread per K tile: one per (row, chunk) of a K-major

@@ -108,56 +108,15 @@ inline bool ln_cols_fused(const LnPath& p, bool vec) {
   return p.K * (vec ? 8 : 1) <= 32;
 }
 
-template <bool VEC>
-__device__ __forceinline__ void ln_load(const uint16_t* p, float* v) {
-  if constexpr (VEC) {
-    const uint4 u = *(const uint4*)p;
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      v[2 * q] = __uint_as_float(w[q] << 16);
-      v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u);
-    }
-  } else {
-    v[0] = bf2f(*p);
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void ln_store(uint16_t* p, const float* v) {
-  if constexpr (VEC) {
-    *(uint4*)p = pack_bf16x8(v);
-  } else {
-    *p = f2bf(v[0]);
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void ln_loadf(const float* p, float* v) {
-  if constexpr (VEC) {
-    const float4 a = ((const float4*)p)[0], b = ((const float4*)p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void ln_storef(float* p, const float* v) {
-  if constexpr (VEC) {
-    ((float4*)p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-    ((float4*)p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-  } else {
-    *p = v[0];
-  }
-}
 // s = float(x) (+ float(r)) of NV columns
 template <bool VEC>
 __device__ __forceinline__ void ln_load_s(const uint16_t* x,
                                           const uint16_t* r, float* v) {
   constexpr int NV = VEC ? 8 : 1;
-  ln_load<VEC>(x, v);
+  ld_bf16<VEC>(x, v);
   if (r) {
     float t[NV];
-    ln_load<VEC>(r, t);
+    ld_bf16<VEC>(r, t);
 #pragma unroll
     for (int j = 0; j < NV; ++j) v[j] += t[j];
   }
@@ -232,12 +191,12 @@ ln_fwd_kernel(const uint16_t* __restrict__ x, long long ldx,
       if (on && cg < CG) {
         const long long c0 = (long long)cg * NV;
         float g[NV], b[NV];
-        ln_loadf<VEC>(gamma + c0, g);
-        ln_loadf<VEC>(beta + c0, b);
+        ld_f32<VEC>(gamma + c0, g);
+        ld_f32<VEC>(beta + c0, b);
 #pragma unroll
         for (int j = 0; j < NV; ++j)
           v[k][j] = __builtin_fmaf(v[k][j] * is, g[j], b[j]);
-        ln_store<VEC>(y + row * ldy + c0, v[k]);
+        st_bf16<VEC>(y + row * ldy + c0, v[k]);
       }
     }
     if (on && lane == 0) {
@@ -299,12 +258,12 @@ ln_fwd_rr_kernel(const uint16_t* __restrict__ x, long long ldx,
         v[0] = sm[cg];
       else
         ln_load_s<VEC>(xr + c0, rr ? rr + c0 : nullptr, v);
-      ln_loadf<VEC>(gamma + c0, g);
-      ln_loadf<VEC>(beta + c0, b);
+      ld_f32<VEC>(gamma + c0, g);
+      ld_f32<VEC>(beta + c0, b);
 #pragma unroll
       for (int j = 0; j < NV; ++j)
         v[j] = __builtin_fmaf((v[j] - mu) * is, g[j], b[j]);
-      ln_store<VEC>(y + row * ldy + c0, v);
+      st_bf16<VEC>(y + row * ldy + c0, v);
     }
     if (threadIdx.x == 0) {
       mean[row] = mu;
@@ -337,7 +296,7 @@ __device__ __forceinline__ void ln_cols_out(float* a, float* comb, int sub,
     }
     __syncthreads();
   }
-  if (sub == 0 && cg < CG) ln_storef<VEC>(wsq + (long long)cg * NV, a);
+  if (sub == 0 && cg < CG) st_f32<VEC>(wsq + (long long)cg * NV, a);
 }
 
 // DX: write dx; COLS: write this workgroup's slice of ws[2][G][C]
@@ -377,7 +336,7 @@ ln_bwd_kernel(const uint16_t* __restrict__ err, long long lde,
         const long long c0 = (long long)cg * NV;
         ln_load_s<VEC>(x + row * ldx + c0, r ? r + row * ldr + c0 : nullptr,
                        v[k]);
-        ln_load<VEC>(err + row * lde + c0, g[k]);
+        ld_bf16<VEC>(err + row * lde + c0, g[k]);
 #pragma unroll
         for (int j = 0; j < NV; ++j) v[k][j] = (v[k][j] - mu) * is;
         if constexpr (COLS) {
@@ -389,7 +348,7 @@ ln_bwd_kernel(const uint16_t* __restrict__ err, long long lde,
         }
         if constexpr (DX) {
           float gm[NV];
-          ln_loadf<VEC>(gamma + c0, gm);
+          ld_f32<VEC>(gamma + c0, gm);
 #pragma unroll
           for (int j = 0; j < NV; ++j) {
             g[k][j] *= gm[j];
@@ -409,7 +368,7 @@ ln_bwd_kernel(const uint16_t* __restrict__ err, long long lde,
 #pragma unroll
           for (int j = 0; j < NV; ++j)
             g[k][j] = is * (g[k][j] - c1 - v[k][j] * c2);
-          ln_store<VEC>(dx + row * lddx + (long long)cg * NV, g[k]);
+          st_bf16<VEC>(dx + row * lddx + (long long)cg * NV, g[k]);
         }
       }
     }
@@ -452,8 +411,8 @@ ln_bwd_rr_dx_kernel(const uint16_t* __restrict__ err, long long lde,
       const long long c0 = (long long)cg * NV;
       float v[NV], g[NV], gm[NV];
       ln_load_s<VEC>(xr + c0, rr ? rr + c0 : nullptr, v);
-      ln_load<VEC>(er + c0, g);
-      ln_loadf<VEC>(gamma + c0, gm);
+      ld_bf16<VEC>(er + c0, g);
+      ld_f32<VEC>(gamma + c0, gm);
 #pragma unroll
       for (int j = 0; j < NV; ++j) {
         const float gh = g[j] * gm[j], sh = (v[j] - mu) * is;
@@ -474,13 +433,13 @@ ln_bwd_rr_dx_kernel(const uint16_t* __restrict__ err, long long lde,
         g[0] = is * (sg[cg] - c1 - sv[cg] * c2);
       } else {
         ln_load_s<VEC>(xr + c0, rr ? rr + c0 : nullptr, v);
-        ln_load<VEC>(er + c0, g);
-        ln_loadf<VEC>(gamma + c0, gm);
+        ld_bf16<VEC>(er + c0, g);
+        ld_f32<VEC>(gamma + c0, gm);
 #pragma unroll
         for (int j = 0; j < NV; ++j)
           g[j] = is * (g[j] * gm[j] - c1 - ((v[j] - mu) * is) * c2);
       }
-      ln_store<VEC>(dx + row * lddx + c0, g);
+      st_bf16<VEC>(dx + row * lddx + c0, g);
     }
   }
 }
@@ -504,7 +463,7 @@ ln_bwd_rr_cols_kernel(const uint16_t* __restrict__ err, long long lde,
     for (long long row = blockIdx.x; row < P; row += gridDim.x) {
       float v[NV], g[NV];
       ln_load_s<VEC>(x + row * ldx + c0, r ? r + row * ldr + c0 : nullptr, v);
-      ln_load<VEC>(err + row * lde + c0, g);
+      ld_bf16<VEC>(err + row * lde + c0, g);
       const float mu = mean[row], is = invstd[row];
 #pragma unroll
       for (int j = 0; j < NV; ++j) {
@@ -512,8 +471,8 @@ ln_bwd_rr_cols_kernel(const uint16_t* __restrict__ err, long long lde,
         a2[j] = __builtin_fmaf(g[j], (v[j] - mu) * is, a2[j]);
       }
     }
-    ln_storef<VEC>(ws + (long long)blockIdx.x * C + c0, a1);
-    ln_storef<VEC>(ws + ((long long)gridDim.x + blockIdx.x) * C + c0, a2);
+    st_f32<VEC>(ws + (long long)blockIdx.x * C + c0, a1);
+    st_f32<VEC>(ws + ((long long)gridDim.x + blockIdx.x) * C + c0, a2);
   }
 }
 
@@ -573,20 +532,17 @@ ln_add_kernel(const uint16_t* a, long long lda, const uint16_t* b,
          cg < CG; cg += stepx) {
       const long long c0 = cg * NV;
       float u[NV], v[NV];
-      ln_load<VEC>(a + row * lda + c0, u);
-      ln_load<VEC>(b + row * ldb + c0, v);
+      ld_bf16<VEC>(a + row * lda + c0, u);
+      ld_bf16<VEC>(b + row * ldb + c0, v);
 #pragma unroll
       for (int j = 0; j < NV; ++j) u[j] += v[j];
-      ln_store<VEC>(out + row * ldo + c0, u);
+      st_bf16<VEC>(out + row * ldo + c0, u);
     }
   }
 }
 
 inline bool ln_shape_ok(long long P, int C) {
   return P >= 1 && C >= 1 && P <= ((1ll << 31) - 1) / C;
-}
-inline bool ln_on16(const void* p, long long ld) {
-  return p == nullptr || ((((uintptr_t)p) & 15) == 0 && ld % 8 == 0);
 }
 
 struct LnFwdArgs {
@@ -666,7 +622,7 @@ HVK_API int hvk_ln_partials(long long P, int C, int vec) {
 // 1 when a [P][C] tensor at x with row pitch ldx (elements) takes the
 // vector path
 HVK_API int hvk_ln_vec(const void* x, long long ldx, int C) {
-  return C % 8 == 0 && ln_on16(x, ldx) ? 1 : 0;
+  return C % 8 == 0 && on16_or_null(x, ldx) ? 1 : 0;
 }
 
 // A/B switch of the backward's column sums: -1 the default rule, 0 a pass
@@ -688,8 +644,8 @@ HVK_API int hvk_ln_fwd(const void* x, long long ldx, const void* r,
   if (!x || !y || !gamma || !beta || !mean || !invstd || !ln_shape_ok(P, C) ||
       ldx < C || ldy < C || (r && ldr < C))
     return -1;
-  const bool vec = C % 8 == 0 && ln_on16(x, ldx) && ln_on16(r, ldr) &&
-                   ln_on16(y, ldy) && ln_on16(gamma, 8) && ln_on16(beta, 8);
+  const bool vec = C % 8 == 0 && on16(x, ldx) && on16_or_null(r, ldr) &&
+                   on16(y, ldy) && on16(gamma, 8) && on16(beta, 8);
   const LnPath p = ln_path(C, vec);
   const LnFwdArgs a = {(const uint16_t*)x, (const uint16_t*)r, (uint16_t*)y,
                        ldx, ldr, ldy, P, C, gamma, beta, eps, mean, invstd};
@@ -726,9 +682,9 @@ HVK_API int hvk_ln_bwd(const void* err, long long lde, const void* x,
       (need_dx && (!dx || lddx < C)))
     return -1;
   if (!need_dx) dx = nullptr;
-  if (vec && !(C % 8 == 0 && ln_on16(err, lde) && ln_on16(x, ldx) &&
-               ln_on16(r, ldr) && ln_on16(dx, lddx) && ln_on16(gamma, 8) &&
-               ln_on16(ws, 8)))
+  if (vec && !(C % 8 == 0 && on16(err, lde) && on16(x, ldx) &&
+               on16_or_null(r, ldr) && on16_or_null(dx, lddx) &&
+               on16(gamma, 8) && on16(ws, 8)))
     return -1;
   const LnPath p = ln_path(C, vec != 0);
   const int G = ln_slices(P, p);
@@ -785,8 +741,8 @@ HVK_API int hvk_add(const void* a, long long lda, const void* b,
                     int C, hipStream_t s) {
   if (!a || !b || !out || !ln_shape_ok(P, C) || lda < C || ldb < C || ldo < C)
     return -1;
-  const bool vec = C % 8 == 0 && ln_on16(a, lda) && ln_on16(b, ldb) &&
-                   ln_on16(out, ldo);
+  const bool vec = C % 8 == 0 && on16(a, lda) && on16(b, ldb) &&
+                   on16(out, ldo);
   long long rows = P, cols = C;
   if (lda == C && ldb == C && ldo == C) {   // one long row
     cols = P * C;

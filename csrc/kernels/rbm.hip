@@ -41,20 +41,6 @@ constexpr int BSUB = 2;           // 16-row batch sub-tiles per sampling tile
 constexpr int TB = 16 * BSUB;     // batch rows per sampling tile
 constexpr int BK = 32;            // K of one MFMA
 
-// the counter hash of elementwise.hip (dropout, stochastic pooling)
-__device__ __forceinline__ uint32_t hash32(uint32_t x, uint32_t seed) {
-  x ^= seed * 0x9E3779B9u;
-  x ^= x >> 16; x *= 0x7feb352du;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
-// plain logistic function; +-inf arguments of the division give exactly 0 / 1
-__device__ __forceinline__ float sigm(float x) {
-  return 1.f / (1.f + __expf(-x));
-}
-
 // The 8 bf16 [row][c .. c + 7] of a row-major operand, 0 outside rows x cols.
 // Unconditional loads (an outside element reads the operand's first element
 // and is replaced by 0 after).  VEC: base and pitch on the 16-B grid and
@@ -385,9 +371,6 @@ rbm_grad_finish(float* grad, const float* __restrict__ ws, long long hv,
   grad[e] = s;
 }
 
-inline bool on_grid(const void* p, long long ld) {
-  return ((uintptr_t)p & 15) == 0 && ld % 8 == 0;
-}
 inline long long r16(long long n) { return (n + 15) / 16 * 16; }
 
 }  // namespace
@@ -421,10 +404,9 @@ HVK_API int hvk_rbm_sample(int transposed, int n, int V, int H, const void* x,
   a.seed = seed;
   a.base = (uint32_t)(unsigned long long)base;
   a.n = n; a.K = K; a.U = U;
-  const bool vec = K % 8 == 0 && U % 8 == 0 && on_grid(x, ldx) &&
-                   on_grid(w, ldw) && ((uintptr_t)bias & 15) == 0 &&
-                   (!probs || on_grid(probs, ldp)) &&
-                   (!sample || on_grid(sample, lds));
+  const bool vec = K % 8 == 0 && U % 8 == 0 && on16(x, ldx) &&
+                   on16(w, ldw) && ((uintptr_t)bias & 15) == 0 &&
+                   on16_or_null(probs, ldp) && on16_or_null(sample, lds);
   const dim3 grid((unsigned)((U + TU - 1) / TU), (unsigned)((n + TB - 1) / TB));
   if (grid.y > 65535u) return -1;
 #define HVK_RBM_SAMPLE(TR, VEC) \
@@ -488,9 +470,9 @@ HVK_API int hvk_rbm_grad(int n, int V, int H, const void* v0, long long ld_v0,
   a.tiles_v = (V + GT - 1) / GT;
   const long long tiles = (long long)((H + GT - 1) / GT) * a.tiles_v;
   if (tiles >= (1ll << 31)) return -1;
-  const bool vec = V % 8 == 0 && H % 8 == 0 && on_grid(v0, ld_v0) &&
-                   on_grid(vk, ld_vk) && on_grid(h0, ld_h0) &&
-                   on_grid(hk, ld_hk);
+  const bool vec = V % 8 == 0 && H % 8 == 0 && on16(v0, ld_v0) &&
+                   on16(vk, ld_vk) && on16(h0, ld_h0) &&
+                   on16(hk, ld_hk);
   const dim3 grid((unsigned)tiles, (unsigned)sp);
 #define HVK_RBM_GRAD(VEC, DIRECT) \
   hipLaunchKernelGGL((rbm_grad_kernel<VEC, DIRECT>), grid, dim3(NTHR), 0, s, a)

@@ -40,11 +40,7 @@ constexpr int BK = 32;            // K of one MFMA
 
 enum { CELL_LSTM = 0, CELL_RNN = 1 };
 
-// plain logistic function and tanh; +-inf arguments of the division give
-// exactly 0 / 1, tanhf saturates to +-1
-__device__ __forceinline__ float sigm(float x) {
-  return 1.f / (1.f + __expf(-x));
-}
+// the cell's tanh (its logistic function is hvk::sigm); saturates to +-1
 __device__ __forceinline__ float tanh_(float x) { return tanhf(x); }
 
 // The 8 bf16 [row][k .. k + 7] of a K-major operand, 0 outside rows x K.  The
@@ -157,10 +153,8 @@ template <bool VEC>
 __device__ __forceinline__ void ld4h(const uint16_t* p, int n, float* v) {
   if constexpr (VEC) {
     const uint2 u = *(const uint2*)p;
-    v[0] = __uint_as_float(u.x << 16);
-    v[1] = __uint_as_float(u.x & 0xffff0000u);
-    v[2] = __uint_as_float(u.y << 16);
-    v[3] = __uint_as_float(u.y & 0xffff0000u);
+    unpack_bf16x2(u.x, v);
+    unpack_bf16x2(u.y, v + 2);
   } else {
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[r] = r < n ? bf2f(p[r]) : 0.f;
@@ -372,10 +366,6 @@ recurrent_fn_kernel(const float* __restrict__ x, float* __restrict__ y,
   if (i < n) y[i] = kind == 0 ? sigm(x[i]) : tanh_(x[i]);
 }
 
-inline bool on_grid(const void* p, long long ld) {
-  return ((uintptr_t)p & 15) == 0 && ld % 8 == 0;
-}
-
 // directions of a launch: one argument block, or a Pair of them
 template <class A>
 constexpr unsigned ndirs(const A&) { return 1; }
@@ -464,11 +454,11 @@ bool fwd_args(FwdArgs& a, bool& vec, int cell, int B, int H,
   a.ld_hp = ld_hp; a.ld_w = ld_w; a.ld_xg = ld_xg; a.ld_cp = ld_cp;
   a.ld_c = ld_c; a.ld_h = ld_h; a.ld_g = ld_g;
   a.B = B; a.H = H;
-  vec = H % 8 == 0 && on_grid(xg, ld_xg) && on_grid(h, ld_h) &&
-        (!h_prev || (on_grid(h_prev, ld_hp) && on_grid(Wh, ld_w))) &&
-        (!lstm || on_grid(c, ld_c)) &&
-        (!a.c_prev || on_grid(c_prev, ld_cp)) &&
-        (!a.gates || on_grid(gates, ld_g));
+  vec = H % 8 == 0 && on16(xg, ld_xg) && on16(h, ld_h) &&
+        (!h_prev || (on16(h_prev, ld_hp) && on16(Wh, ld_w))) &&
+        (!lstm || on16(c, ld_c)) &&
+        (!a.c_prev || on16(c_prev, ld_cp)) &&
+        (!a.gates || on16(gates, ld_g));
   return true;
 }
 
@@ -553,12 +543,12 @@ bool bwd_args(BwdArgs& a, bool& vec, int cell, int B, int H,
   a.ld_cp = ld_cp; a.ld_c = ld_c; a.ld_dci = ld_dci; a.ld_dco = ld_dco;
   a.ld_dg = ld_dg;
   a.B = B; a.H = H;
-  vec = H % 8 == 0 && on_grid(dg, ld_dg) && on_grid(gates, ld_g) &&
-        (!dg_next || (on_grid(dg_next, ld_dgn) && on_grid(WhT, ld_wt))) &&
-        (!err || on_grid(err, ld_e)) &&
-        (!lstm || (on_grid(c, ld_c) && on_grid(dc_out, ld_dco))) &&
-        (!a.c_prev || on_grid(c_prev, ld_cp)) &&
-        (!a.dc_in || on_grid(dc_in, ld_dci));
+  vec = H % 8 == 0 && on16(dg, ld_dg) && on16(gates, ld_g) &&
+        (!dg_next || (on16(dg_next, ld_dgn) && on16(WhT, ld_wt))) &&
+        on16_or_null(err, ld_e) &&
+        (!lstm || (on16(c, ld_c) && on16(dc_out, ld_dco))) &&
+        (!a.c_prev || on16(c_prev, ld_cp)) &&
+        (!a.dc_in || on16(dc_in, ld_dci));
   return true;
 }
 
@@ -845,11 +835,11 @@ bool gru_fwd_args(GruFwdArgs& a, bool& vec, int B, int H, const void* h_prev,
   a.ld_hp = ld_hp; a.ld_w = ld_w; a.ld_xg = ld_xg; a.ld_hfp = ld_hfp;
   a.ld_hf = ld_hf; a.ld_hn = ld_hn; a.ld_h = ld_h; a.ld_g = ld_g;
   a.B = B; a.H = H;
-  vec = H % 8 == 0 && on_grid(xg, ld_xg) && on_grid(h, ld_h) &&
-        on_grid(hf, ld_hf) && on_grid(hn, ld_hn) &&
-        (!h_prev || (on_grid(h_prev, ld_hp) && on_grid(Wh, ld_w))) &&
-        (!hf_prev || on_grid(hf_prev, ld_hfp)) &&
-        (!bhn || on_grid(bhn, 8)) && (!gates || on_grid(gates, ld_g));
+  vec = H % 8 == 0 && on16(xg, ld_xg) && on16(h, ld_h) &&
+        on16(hf, ld_hf) && on16(hn, ld_hn) &&
+        (!h_prev || (on16(h_prev, ld_hp) && on16(Wh, ld_w))) &&
+        on16_or_null(hf_prev, ld_hfp) && on16_or_null(bhn, 8) &&
+        on16_or_null(gates, ld_g);
   return true;
 }
 
@@ -936,13 +926,12 @@ bool gru_bwd_args(GruBwdArgs& a, bool& vec, int B, int H,
   a.ld_hn = ld_hn; a.ld_hfp = ld_hfp; a.ld_dci = ld_dci; a.ld_dco = ld_dco;
   a.ld_dgx = ld_dgx; a.ld_dgh = ld_dgh;
   a.B = B; a.H = H;
-  vec = H % 8 == 0 && on_grid(dgx, ld_dgx) && on_grid(dgh, ld_dgh) &&
-        on_grid(gates, ld_g) && on_grid(hn, ld_hn) &&
-        on_grid(dc_out, ld_dco) &&
-        (!dgh_next || (on_grid(dgh_next, ld_dgn) && on_grid(WhT, ld_wt))) &&
-        (!err || on_grid(err, ld_e)) &&
-        (!hf_prev || on_grid(hf_prev, ld_hfp)) &&
-        (!dc_in || on_grid(dc_in, ld_dci));
+  vec = H % 8 == 0 && on16(dgx, ld_dgx) && on16(dgh, ld_dgh) &&
+        on16(gates, ld_g) && on16(hn, ld_hn) &&
+        on16(dc_out, ld_dco) &&
+        (!dgh_next || (on16(dgh_next, ld_dgn) && on16(WhT, ld_wt))) &&
+        on16_or_null(err, ld_e) && on16_or_null(hf_prev, ld_hfp) &&
+        on16_or_null(dc_in, ld_dci);
   return true;
 }
 

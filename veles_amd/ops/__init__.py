@@ -66,6 +66,17 @@ def _lib_call(name, *args):
     _lib.check(fn(*args), name)
 
 
+def _fn(name):
+    """Entry point ``name`` of the kernel library; a library built before
+    the entry point existed is an error, never a fall-back."""
+    fn = getattr(_lib.lib(), name, None)
+    if fn is None:
+        raise _lib.KernelLibraryMissing(
+            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
+            (_lib.LIB_PATH, name))
+    return fn
+
+
 def _gpu(t):
     return t is not None and t.is_cuda
 
@@ -1758,20 +1769,11 @@ def lrn_bwd(x, dy, n=5, alpha=1e-4, beta=0.75, k=2.0, aux=None, aux_act=0,
 BN_CPU_CHAIN = 64     # CPU path: float32 sums of 64 rows, then of those
 
 
-def _bn_fn(name):
-    fn = getattr(_lib.lib(), name, None)
-    if fn is None:
-        raise _lib.KernelLibraryMissing(
-            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
-            (_lib.LIB_PATH, name))
-    return fn
-
-
 def bn_partials(P, C, vec):
     """Partials per channel of the two-launch reductions of ``hvk_bn_stats``
     and ``hvk_bn_bwd`` over [P][C]: a function of the shape and the path
     (``vec``: 8 channels per lane) only, never of the device."""
-    g = _bn_fn("hvk_bn_partials")(int(P), int(C), int(bool(vec)))
+    g = _fn("hvk_bn_partials")(int(P), int(C), int(bool(vec)))
     if g < 1:
         raise ValueError("batchnorm: no grid for P = %d, C = %d, vec = %s" %
                          (P, C, vec))
@@ -1844,8 +1846,10 @@ def _bn_xdtype(name, x):
             name, want, x.device.type, x.dtype))
 
 
-def _bn_vec(C, *pairs):
-    fn = _bn_fn("hvk_bn_vec")
+def _vec8(probe, C, *pairs):
+    """True when every present (tensor, pitch) pair takes the 8-wide path of
+    the family whose predicate is the library's ``probe``"""
+    fn = _fn(probe)
     return C % 8 == 0 and all(
         t is None or fn(_p(t), int(ld), C) for t, ld in pairs)
 
@@ -1891,19 +1895,19 @@ def batchnorm_fwd(x, gamma, beta, running_mean, running_var, training=True,
     if _gpu(x):
         s = _s(x)
         if training:
-            vec = _bn_vec(C, (x, ldx))
+            vec = _vec8("hvk_bn_vec", C, (x, ldx))
             G = bn_partials(P, C, vec)
             w = _rec_buf(ws, "stats", (2 * C * G,), torch.float32, dev)
-            _lib.check(_bn_fn("hvk_bn_stats")(
+            _lib.check(_fn("hvk_bn_stats")(
                 _p(x), ldx, P, C, int(vec), _p(gamma), _p(beta),
                 _p(running_mean), _p(running_var), float(eps),
                 float(momentum), _p(mean), _p(invstd), _p(table), _p(w), s),
                 "hvk_bn_stats")
         else:
-            _lib.check(_bn_fn("hvk_bn_fold")(
+            _lib.check(_fn("hvk_bn_fold")(
                 _p(gamma), _p(beta), _p(running_mean), _p(running_var), C,
                 float(eps), _p(table), s), "hvk_bn_fold")
-        _lib.check(_bn_fn("hvk_bn_apply")(
+        _lib.check(_fn("hvk_bn_apply")(
             _p(x), ldx, _p(out), ldy, P, C, _p(table), act, s),
             "hvk_bn_apply")
         return out
@@ -1980,12 +1984,12 @@ def batchnorm_bwd(err, x, y, gamma, save, dgamma, dbeta, act=0,
     ws = {} if ws is None else ws
     mean, invstd = save["mean"], save["invstd"]
     if _gpu(x):
-        vec = _bn_vec(C, (x, ldx), (err, lde), (y, ldy), (aux, lda),
-                      (out, lddx))
+        vec = _vec8("hvk_bn_vec", C, (x, ldx), (err, lde), (y, ldy),
+                    (aux, lda), (out, lddx))
         G = bn_partials(P, C, vec)
         w = _rec_buf(ws, "bwd", (2 * C * G,), torch.float32, dev)
         coef = _rec_buf(ws, "coef", (3, C), torch.float32, dev)
-        _lib.check(_bn_fn("hvk_bn_bwd")(
+        _lib.check(_fn("hvk_bn_bwd")(
             _p(x), ldx, _p(err), lde, _p(y), ldy, _p(aux), lda, _p(out),
             lddx, P, C, int(vec), _p(gamma), _p(mean), _p(invstd),
             _p(dgamma), _p(dbeta), int(accumulate is True), act, aux_act,
@@ -2020,7 +2024,7 @@ def ln_partials(P, C, vec):
     """Slices per column of the column sums (dgamma, dbeta) of
     ``hvk_ln_bwd`` over [P][C]: a function of the shape and the path
     (``vec``: 8 columns per lane) only, never of the device."""
-    g = _bn_fn("hvk_ln_partials")(int(P), int(C), int(bool(vec)))
+    g = _fn("hvk_ln_partials")(int(P), int(C), int(bool(vec)))
     if g < 1:
         raise ValueError("layernorm: no grid for P = %d, C = %d, vec = %s" %
                          (P, C, vec))
@@ -2036,12 +2040,6 @@ def _ln_row_sum(t):
             t = F.pad(t, (0, pad))
         t = t.reshape(t.shape[0], -1, LN_CPU_CHAIN).sum(2)
     return t[:, 0]
-
-
-def _ln_vec(C, *pairs):
-    fn = _bn_fn("hvk_ln_vec")
-    return C % 8 == 0 and all(
-        t is None or fn(_p(t), int(ld), C) for t, ld in pairs)
 
 
 def layernorm_fwd(x, gamma, beta, *, residual=None, eps=1e-5, save=None,
@@ -2072,7 +2070,7 @@ def layernorm_fwd(x, gamma, beta, *, residual=None, eps=1e-5, save=None,
     mean = _rec_buf(save, "mean", (P,), torch.float32, dev)
     invstd = _rec_buf(save, "invstd", (P,), torch.float32, dev)
     if _gpu(x):
-        _lib.check(_bn_fn("hvk_ln_fwd")(
+        _lib.check(_fn("hvk_ln_fwd")(
             _p(x), ldx, _p(residual), ldr, _p(out), ldy, P, C, _p(gamma),
             _p(beta), float(eps), _p(mean), _p(invstd), _s(x)), "hvk_ln_fwd")
         return out
@@ -2121,11 +2119,11 @@ def layernorm_bwd(err, x, gamma, save, dgamma, dbeta, *, residual=None,
     ws = {} if ws is None else ws
     mean, invstd = save["mean"], save["invstd"]
     if _gpu(x):
-        vec = _ln_vec(C, (err, lde), (x, ldx), (residual, ldr), (out, lddx),
-                      (gamma, 8))
+        vec = _vec8("hvk_ln_vec", C, (err, lde), (x, ldx), (residual, ldr),
+                    (out, lddx), (gamma, 8))
         G = ln_partials(P, C, vec)
         w = _rec_buf(ws, "bwd", (2 * C * G,), torch.float32, dev)
-        _lib.check(_bn_fn("hvk_ln_bwd")(
+        _lib.check(_fn("hvk_ln_bwd")(
             _p(err), lde, _p(x), ldx, _p(residual), ldr, _p(out), lddx, P, C,
             int(vec), _p(gamma), _p(mean), _p(invstd), _p(dgamma),
             _p(dbeta), int(accumulate is True), int(bool(need_dx)), _p(w),
@@ -2166,7 +2164,7 @@ def add(a, b, out=None):
         out = torch.empty(a.shape, dtype=a.dtype, device=a.device)
     _, _, ldo = _bn_rows(name, "out", out, like=a)
     if _gpu(a):
-        _lib.check(_bn_fn("hvk_add")(
+        _lib.check(_fn("hvk_add")(
             _p(a), lda, _p(b), ldb, _p(out), ldo, P, C, _s(a)), "hvk_add")
         return out
     torch.add(a, b, out=out)
@@ -2660,6 +2658,10 @@ def solver_update(w, grad, s1, s2, segs, w_lp=None, gscale=1.0,
 
 
 # ---------------------------------------------------------------- dropout
+# The Python mirror of hvk::hash32 in csrc/kernels/hvk_common.h, the counter
+# hash behind every mask and sample of the kernel library: the two change
+# together, or a CPU pass and the ranks of a data-parallel step stop drawing
+# the bits of a single GPU process.
 def _hash32(i, seed):
     M = 0xFFFFFFFF
     x = i ^ ((seed * 0x9E3779B9) & M)
@@ -3007,15 +3009,6 @@ def _kohonen_out(name, what, t, dtype, size, device):
     return t
 
 
-def _kohonen_fn(name):
-    fn = getattr(_lib.lib(), name, None)
-    if fn is None:
-        raise _lib.KernelLibraryMissing(
-            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
-            (_lib.LIB_PATH, name))
-    return fn
-
-
 def kohonen_argmin(x, w, n=None, argmin=None, qerr=None, winners=None,
                    splits=0):
     """Winners of the first ``n`` rows of ``x`` on the map ``w`` (float32
@@ -3040,7 +3033,7 @@ def kohonen_argmin(x, w, n=None, argmin=None, qerr=None, winners=None,
         nt = -(-NN // _KOH_TILE)
         sp = max(1, min(splits or _KOH_WGS // tb, nt))
         ws = _grow_ws("kohonen_argmin", (2 * sp + 1) * n, torch.float32, dev)
-        _lib.check(_kohonen_fn("hvk_kohonen_argmin")(
+        _lib.check(_fn("hvk_kohonen_argmin")(
             _p(x2), DT[x2.dtype], _p(w), n, NN, D, D, _p(argmin), _p(qerr),
             _p(winners), _p(ws), sp, _s(w)), "hvk_kohonen_argmin")
         return argmin[:n]
@@ -3085,7 +3078,7 @@ def kohonen_update(x, w, coords, argmin, sigma, gradient, n=None, splits=0):
         sp = max(1, min(sp, nk))
         ws = None if sp == 1 else _grow_ws(
             "kohonen_update", sp * NN * (D + 1), torch.float32, dev)
-        _lib.check(_kohonen_fn("hvk_kohonen_update")(
+        _lib.check(_fn("hvk_kohonen_update")(
             _p(x2), DT[x2.dtype], _p(w), _p(coords), _p(argmin), n, NN, D, D,
             inv2s2, gradient / n, _p(ws), sp, _s(w)), "hvk_kohonen_update")
         return w
@@ -3107,13 +3100,7 @@ def _r8(n):
     return -(-n // 8) * 8
 
 
-def _rec_fn(name):
-    fn = getattr(_lib.lib(), name, None)
-    if fn is None:
-        raise _lib.KernelLibraryMissing(
-            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
-            (_lib.LIB_PATH, name))
-    return fn
+_rec_fn = _fn   # the recurrent GPU tests look entry points up by this name
 
 
 def _rec_buf(store, key, shape, dtype, dev, zero=False):
@@ -3128,20 +3115,26 @@ def _rec_buf(store, key, shape, dtype, dev, zero=False):
     return t
 
 
-def _lstm_args(name, x, w, bias, H, cell, D):
-    """Shared host checks of lstm_fwd / lstm_bwd over ``D`` directions;
-    returns (B, T, I, H, kernel cell code, gates)."""
+def _cell(name, cell):
+    """(kernel code, gates) of an lstm_fwd / lstm_bwd cell"""
     if cell not in _CELLS:
         raise ValueError("%s: unknown cell %r (lstm, rnn)" % (name, cell))
-    code, ng = _CELLS[cell]
+    return _CELLS[cell]
+
+
+def _rec_args(name, x, w, bias, H, D, ng, nbias, cell=None, bias_parts=""):
+    """Shared host checks of lstm_* / gru_* over ``D`` directions of ``ng``
+    gates with ``nbias`` bias blocks; ``cell`` and ``bias_parts`` are words
+    of the messages.  Returns (B, T, I, H)."""
     H = int(H)
     if x.dim() != 3 or min(x.shape) < 1:
         raise ValueError("%s: input must be [B][T][I], got %s" %
                          (name, tuple(x.shape)))
     B, T, I = x.shape
     if H < 1 or w.dim() != 2 or tuple(w.shape) != (D * ng * H, I + H):
-        raise ValueError("%s: weights must be [%d][%d] (%s, I = %d, H = %d), "
-                         "got %s" % (name, D * ng * H, I + H, cell, I, H,
+        raise ValueError("%s: weights must be [%d][%d] (%sI = %d, H = %d), "
+                         "got %s" % (name, D * ng * H, I + H,
+                                     "%s, " % cell if cell else "", I, H,
                                      tuple(w.shape)))
     if x.device != w.device or (bias is not None and bias.device != w.device):
         raise ValueError("%s: operands on different devices" % name)
@@ -3149,10 +3142,10 @@ def _lstm_args(name, x, w, bias, H, cell, D):
         raise ValueError("%s: input rows must be contiguous with one pitch "
                          "over [B][T], weight rows contiguous (strides %s, "
                          "%s)" % (name, x.stride(), w.stride()))
-    if bias is not None and (tuple(bias.shape) != (D * ng * H,) or
+    if bias is not None and (tuple(bias.shape) != (D * nbias * H,) or
                              not bias.is_contiguous()):
-        raise ValueError("%s: bias must be a contiguous [%d], got %s" %
-                         (name, D * ng * H, tuple(bias.shape)))
+        raise ValueError("%s: bias must be a contiguous [%d]%s, got %s" %
+                         (name, D * nbias * H, bias_parts, tuple(bias.shape)))
     if _gpu(w):
         if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
             raise TypeError("%s: GPU input and weights must be bfloat16, got "
@@ -3168,53 +3161,12 @@ def _lstm_args(name, x, w, bias, H, cell, D):
     if B * T * max(_r8(D * ng * H), x.stride(1)) >= 1 << 31:
         raise ValueError("%s: %d x %d x %d exceeds 2^31 elements" %
                          (name, B, T, max(D * ng * H, I)))
-    return B, T, I, H, code, ng
+    return B, T, I, H
 
 
 def _rows(x, B, T):
     """[B][T][I] with one row pitch as a [B*T][I] view (no copy)"""
     return x.as_strided((B * T, x.shape[2]), (x.stride(1), 1))
-
-
-def _gru_args(name, x, w, bias, H, D):
-    """Shared host checks of gru_fwd / gru_bwd over ``D`` directions; returns
-    (B, T, I, H)."""
-    H = int(H)
-    if x.dim() != 3 or min(x.shape) < 1:
-        raise ValueError("%s: input must be [B][T][I], got %s" %
-                         (name, tuple(x.shape)))
-    B, T, I = x.shape
-    if H < 1 or w.dim() != 2 or tuple(w.shape) != (D * 3 * H, I + H):
-        raise ValueError("%s: weights must be [%d][%d] (I = %d, H = %d), "
-                         "got %s" % (name, D * 3 * H, I + H, I, H,
-                                     tuple(w.shape)))
-    if x.device != w.device or (bias is not None and bias.device != w.device):
-        raise ValueError("%s: operands on different devices" % name)
-    if x.stride(2) != 1 or x.stride(0) != T * x.stride(1) or w.stride(1) != 1:
-        raise ValueError("%s: input rows must be contiguous with one pitch "
-                         "over [B][T], weight rows contiguous (strides %s, "
-                         "%s)" % (name, x.stride(), w.stride()))
-    if bias is not None and (tuple(bias.shape) != (D * 4 * H,) or
-                             not bias.is_contiguous()):
-        raise ValueError("%s: bias must be a contiguous [%d] = (b_r, b_z, "
-                         "b_n, b_hn) per direction, got %s" %
-                         (name, D * 4 * H, tuple(bias.shape)))
-    if _gpu(w):
-        if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
-            raise TypeError("%s: GPU input and weights must be bfloat16, got "
-                            "%s / %s" % (name, x.dtype, w.dtype))
-        if bias is not None and bias.dtype != torch.float32:
-            raise TypeError("%s: GPU bias must be float32, got %s" %
-                            (name, bias.dtype))
-        if x.data_ptr() % 2 or w.data_ptr() % 2:
-            raise ValueError("%s: operands off the element grid" % name)
-    elif not (x.is_floating_point() and w.is_floating_point()):
-        raise TypeError("%s: floating-point operands, got %s / %s" %
-                        (name, x.dtype, w.dtype))
-    if B * T * max(_r8(D * 3 * H), x.stride(1)) >= 1 << 31:
-        raise ValueError("%s: %d x %d x %d exceeds 2^31 elements" %
-                         (name, B, T, max(D * 3 * H, I)))
-    return B, T, I, H
 
 
 # Directions (docs/OPS.md "Bidirectional"): every pass below is written once,
@@ -3391,7 +3343,8 @@ def lstm_fwd(x, w, bias, H, *, cell="lstm", return_sequences=False,
     name = "lstm_fwd"
     dirs = _directions(name, direction)
     D = len(dirs)
-    B, T, I, H, code, ng = _lstm_args(name, x, w, bias, H, cell, D)
+    code, ng = _cell(name, cell)
+    B, T, I, H = _rec_args(name, x, w, bias, H, D, ng, ng, cell)
     dev = x.device
     st = save if save is not None else (ws if ws is not None else {})
     gh = ng * H
@@ -3400,8 +3353,8 @@ def lstm_fwd(x, w, bias, H, *, cell="lstm", return_sequences=False,
     if not return_sequences:
         _rec_out_check(name, out, B, DH, dev)
     if _gpu(x):
-        fn1 = _rec_fn("hvk_lstm_step_fwd")
-        fn2 = _rec_fn("hvk_lstm_step_fwd2") if D == 2 else None
+        fn1 = _fn("hvk_lstm_step_fwd")
+        fn2 = _fn("hvk_lstm_step_fwd2") if D == 2 else None
         PW = _r8(W)
         xg_ = _rec_buf(st, "_xg", (B, T, PW), torch.float32, dev)
         h_all = _rec_buf(st, "h", (B, T, DH), torch.bfloat16, dev)
@@ -3493,13 +3446,11 @@ def lstm_bwd(err, x, w, save, dw, dbias, *, cell="lstm", accumulate="overwrite",
     name = "lstm_bwd"
     dirs = _directions(name, direction)
     D = len(dirs)
-    if cell not in _CELLS:
-        raise ValueError("%s: unknown cell %r (lstm, rnn)" % (name, cell))
-    ng = _CELLS[cell][1]
+    code, ng = _cell(name, cell)
     if w.dim() != 2 or w.shape[0] % (D * ng):
         raise ValueError("%s: weights %s" % (name, tuple(w.shape)))
-    B, T, I, H, code, ng = _lstm_args(name, x, w, None,
-                                      w.shape[0] // (D * ng), cell, D)
+    B, T, I, H = _rec_args(name, x, w, None, w.shape[0] // (D * ng), D, ng,
+                           ng, cell)
     dev = x.device
     gh = ng * H
     W, DH = D * gh, D * H
@@ -3518,8 +3469,8 @@ def lstm_bwd(err, x, w, save, dw, dbias, *, cell="lstm", accumulate="overwrite",
         if err.dtype != torch.bfloat16:
             raise TypeError("%s: GPU err must be bfloat16, got %s" %
                             (name, err.dtype))
-        fn1 = _rec_fn("hvk_lstm_step_bwd")
-        fn2 = _rec_fn("hvk_lstm_step_bwd2") if D == 2 else None
+        fn1 = _fn("hvk_lstm_step_bwd")
+        fn2 = _fn("hvk_lstm_step_bwd2") if D == 2 else None
         P, PW = _r8(gh), _r8(W)
         if lstm:
             g_ = _rec_gates_check(name, "lstm_fwd", save, (B, T, PW))
@@ -3637,7 +3588,9 @@ def gru_fwd(x, w, bias, H, *, return_sequences=False, save=None, out=None,
     name = "gru_fwd"
     dirs = _directions(name, direction)
     D = len(dirs)
-    B, T, I, H = _gru_args(name, x, w, bias, H, D)
+    B, T, I, H = _rec_args(
+        name, x, w, bias, H, D, 3, 4,
+        bias_parts=" = (b_r, b_z, b_n, b_hn) per direction")
     dev = x.device
     st = save if save is not None else (ws if ws is not None else {})
     gh = 3 * H
@@ -3645,8 +3598,8 @@ def gru_fwd(x, w, bias, H, *, return_sequences=False, save=None, out=None,
     if not return_sequences:
         _rec_out_check(name, out, B, DH, dev)
     if _gpu(x):
-        fn1 = _rec_fn("hvk_gru_step_fwd")
-        fn2 = _rec_fn("hvk_gru_step_fwd2") if D == 2 else None
+        fn1 = _fn("hvk_gru_step_fwd")
+        fn2 = _fn("hvk_gru_step_fwd2") if D == 2 else None
         PW = _r8(W)
         xg_ = _rec_buf(st, "_xg", (B, T, PW), torch.float32, dev)
         h_all = _rec_buf(st, "h", (B, T, DH), torch.bfloat16, dev)
@@ -3740,7 +3693,7 @@ def gru_bwd(err, x, w, save, dw, dbias, *, accumulate="overwrite",
     D = len(dirs)
     if w.dim() != 2 or w.shape[0] % (3 * D):
         raise ValueError("%s: weights %s" % (name, tuple(w.shape)))
-    B, T, I, H = _gru_args(name, x, w, None, w.shape[0] // (3 * D), D)
+    B, T, I, H = _rec_args(name, x, w, None, w.shape[0] // (3 * D), D, 3, 4)
     dev = x.device
     gh = 3 * H
     W, DH = D * gh, D * H
@@ -3758,8 +3711,8 @@ def gru_bwd(err, x, w, save, dw, dbias, *, accumulate="overwrite",
         if err.dtype != torch.bfloat16:
             raise TypeError("%s: GPU err must be bfloat16, got %s" %
                             (name, err.dtype))
-        fn1 = _rec_fn("hvk_gru_step_bwd")
-        fn2 = _rec_fn("hvk_gru_step_bwd2") if D == 2 else None
+        fn1 = _fn("hvk_gru_step_bwd")
+        fn2 = _fn("hvk_gru_step_bwd2") if D == 2 else None
         P, PW = _r8(gh), _r8(W)
         g_ = _rec_gates_check(name, "gru_fwd", save, (B, T, PW))
         # Wh^T of every direction, one copy per call: the product of a step
@@ -3854,15 +3807,6 @@ def gru_bwd(err, x, w, save, dw, dbias, *, accumulate="overwrite",
 
 # ------------------------------------------- restricted Boltzmann machines
 # docs/OPS.md "Restricted Boltzmann machines"; kernels in csrc/kernels/rbm.hip.
-def _rbm_fn(name):
-    fn = getattr(_lib.lib(), name, None)
-    if fn is None:
-        raise _lib.KernelLibraryMissing(
-            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
-            (_lib.LIB_PATH, name))
-    return fn
-
-
 def rbm_layout(V, H):
     """(offset of hbias, offset of vbias, length) of the flat float32 buffer
     [W [H][V] | hbias [H] | vbias [V]]: every segment starts on a 16-element
@@ -3966,7 +3910,7 @@ def rbm_sample(x, w, bias, *, transposed=False, n=None, probs=None,
         raise ValueError("%s: seed_dev must be an int32 [1] on %s" %
                          (name, dev))
     if gpu:
-        _lib.check(_rbm_fn("hvk_rbm_sample")(
+        _lib.check(_fn("hvk_rbm_sample")(
             1 if transposed else 0, n, V, H, _p(x), ldx, _p(w), ldw,
             _p(bias), _p(probs), ldp, _p(sample), lds,
             int(seed) & 0xFFFFFFFF, _p(seed_dev), base & 0xFFFFFFFF, _s(w)),
@@ -4032,12 +3976,12 @@ def rbm_grad(v0, h0, vk, hk, grad, *, n=None, scale=None, splits=0):
         raise ValueError("%s: splits %d" % (name, splits))
     scale = -1.0 / n if scale is None else float(scale)
     if gpu:
-        sp = _rbm_fn("hvk_rbm_grad_splits")(n, V, H, splits)
+        sp = _fn("hvk_rbm_grad_splits")(n, V, H, splits)
         if sp < 1 or sp > 65535:
             raise ValueError("%s: %d splits for %d rows" % (name, splits, n))
         ws = None if sp == 1 else _grow_ws("rbm_grad", sp * total,
                                            torch.float32, dev)
-        _lib.check(_rbm_fn("hvk_rbm_grad")(
+        _lib.check(_fn("hvk_rbm_grad")(
             n, V, H, _p(v0), ld_v0, _p(h0), ld_h0, _p(vk), ld_vk, _p(hk),
             ld_hk, _p(grad), scale, _p(ws), sp, _s(grad)), "hvk_rbm_grad")
         return grad
@@ -4056,15 +4000,6 @@ def rbm_grad(v0, h0, vk, hk, grad, *, n=None, scale=None, splits=0):
 ATTN_HEAD_DIMS = (32, 64, 128)
 ATTN_TQ = 128
 ATTN_TK = 32
-
-
-def _attn_fn(name):
-    fn = getattr(_lib.lib(), name, None)
-    if fn is None:
-        raise _lib.KernelLibraryMissing(
-            "%s lacks %s - rebuild with python -m veles_amd.ops.build" %
-            (_lib.LIB_PATH, name))
-    return fn
 
 
 def attn_head_dim(E, heads, name="attention"):
@@ -4276,18 +4211,18 @@ def attention_fwd(q, k, v, heads, causal=False, out=None, save=None,
     p, sd, sv = _attn_drop(name, q, dropout, seed, seed_dev, save)
     if _gpu(q):
         if G > 1:
-            _lib.check(_attn_fn("hvk_gqa_fwd")(
+            _lib.check(_fn("hvk_gqa_fwd")(
                 _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, _p(lse), B,
                 T, NH, KVH, D, int(bool(causal)), _p(sd), p, int(base_row),
                 _s(q)), "hvk_gqa_fwd")
             return out
         if p:
-            _lib.check(_attn_fn("hvk_adrop_fwd")(
+            _lib.check(_fn("hvk_adrop_fwd")(
                 _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, _p(lse), B,
                 T, NH, D, int(bool(causal)), _p(sd), p, int(base_row),
                 _s(q)), "hvk_adrop_fwd")
             return out
-        _lib.check(_attn_fn("hvk_attn_fwd")(
+        _lib.check(_fn("hvk_attn_fwd")(
             _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo, _p(lse), B, T,
             NH, D, int(bool(causal)), _s(q)), "hvk_attn_fwd")
         return out
@@ -4361,34 +4296,34 @@ def attention_bwd(do, q, k, v, o, save, heads, causal=False, dq=None,
     p, sd, sv = _attn_drop(name, q, dropout, seed, seed_dev, ws)
     if _gpu(q):
         s = _s(q)
-        _lib.check(_attn_fn("hvk_attn_bwd_delta")(
+        _lib.check(_fn("hvk_attn_bwd_delta")(
             _p(do), lddo, _p(o), ldo, _p(delta), B, T, NH, D, s),
             "hvk_attn_bwd_delta")
         if G > 1:
             tail = (B, T, NH, KVH, D, c, _p(sd), p, int(base_row), s)
-            _lib.check(_attn_fn("hvk_gqa_bwd_dkv")(
+            _lib.check(_fn("hvk_gqa_bwd_dkv")(
                 _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
                 _p(delta), _p(dk), lddk, _p(dv), lddv, *tail),
                 "hvk_gqa_bwd_dkv")
-            _lib.check(_attn_fn("hvk_gqa_bwd_dq")(
+            _lib.check(_fn("hvk_gqa_bwd_dq")(
                 _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
                 _p(delta), _p(dq), lddq, *tail), "hvk_gqa_bwd_dq")
             return dq, dk, dv
         if p:
             tail = (B, T, NH, D, c, _p(sd), p, int(base_row), s)
-            _lib.check(_attn_fn("hvk_adrop_bwd_dkv")(
+            _lib.check(_fn("hvk_adrop_bwd_dkv")(
                 _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
                 _p(delta), _p(dk), lddk, _p(dv), lddv, *tail),
                 "hvk_adrop_bwd_dkv")
-            _lib.check(_attn_fn("hvk_adrop_bwd_dq")(
+            _lib.check(_fn("hvk_adrop_bwd_dq")(
                 _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
                 _p(delta), _p(dq), lddq, *tail), "hvk_adrop_bwd_dq")
             return dq, dk, dv
-        _lib.check(_attn_fn("hvk_attn_bwd_dkv")(
+        _lib.check(_fn("hvk_attn_bwd_dkv")(
             _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
             _p(delta), _p(dk), lddk, _p(dv), lddv, B, T, NH, D, c, s),
             "hvk_attn_bwd_dkv")
-        _lib.check(_attn_fn("hvk_attn_bwd_dq")(
+        _lib.check(_fn("hvk_attn_bwd_dq")(
             _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(do), lddo, _p(lse),
             _p(delta), _p(dq), lddq, B, T, NH, D, c, s), "hvk_attn_bwd_dq")
         return dq, dk, dv
@@ -4654,7 +4589,7 @@ def ffn_act_code(act):
 def ffn_partials(P, F, transposed):
     """Slabs per column of ``hvk_ffn_act_bwd``'s column sums over [P][F]: a
     function of the shape and of whether du^T is written only."""
-    g = _bn_fn("hvk_ffn_act_partials")(int(P), int(F), int(bool(transposed)))
+    g = _fn("hvk_ffn_act_partials")(int(P), int(F), int(bool(transposed)))
     if g < 1:
         raise ValueError("ffn: no grid for P = %d, F = %d, transposed = %s" %
                          (P, F, transposed))
@@ -4697,7 +4632,7 @@ def ffn_act_fwd(u, act="gelu", out=None):
         out = torch.empty(u.shape, dtype=u.dtype, device=u.device)
     _, _, ldh = _bn_rows(name, "out", out, like=u)
     if _gpu(u):
-        _lib.check(_bn_fn("hvk_ffn_act_fwd")(
+        _lib.check(_fn("hvk_ffn_act_fwd")(
             _p(u), ldu, _p(out), ldh, P, F_, code, _s(u)), "hvk_ffn_act_fwd")
         return out
     out.copy_(ffn_act_ref(u, act))
@@ -4741,7 +4676,7 @@ def ffn_act_bwd(dh, u, act="gelu", *, out=None, out_t=None, db1=None,
         ws = {} if ws is None else ws
         G = ffn_partials(P, F_, out_t is not None)
         w = _rec_buf(ws, "act_bwd", (F_ * G,), torch.float32, u.device)
-        _lib.check(_bn_fn("hvk_ffn_act_bwd")(
+        _lib.check(_fn("hvk_ffn_act_bwd")(
             _p(dh), lddh, _p(u), ldu, _p(out), lddu, _p(out_t), lddut, P, F_,
             code, _p(db1), int(accumulate is True), _p(w), _s(u)),
             "hvk_ffn_act_bwd")
